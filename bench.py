@@ -1,6 +1,15 @@
 """Benchmark: GCNConv F=256 aggregation (PyG 1.4.3 propagate, fused on MI355X).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload rmat21|products]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--full adds everything else the line can carry, each measured after the timed
+region in runs of its own: the CPU baseline, the reference's device path and
+the vendor SpMM, the x @ W GEMM, the GAT kernel's own timing and, N > 1, the
+build split, the step taken apart, the compute in turn and the link model.
+--dump-outputs DIR writes what the last timed step computed (a fixed, seeded
+sample of its rows) as DIR/<name>.npy.
     torchrun --nproc-per-node N bench.py --gpus N ...     (driver, N > 1)
 
 --gpus N > 1 without a launcher (RANK unset): bench.py starts the N rank
@@ -29,8 +38,8 @@ Workloads (one GCNConv propagate per step, F = 256, fp32):
            (ShardedGraph.gat_propagate) -- metric: GAT edges/s.
 One step = the fused gather * norm -> segment-sum + bias HIP kernel (plus its
 split-row fix-up) over all E' edges.  The CSR / schedule / norm build
-(one-time, cached=True semantics) and the x @ W GEMM are timed separately and
-reported beside the metric.
+(one-time, cached=True semantics) is timed separately and reported beside
+the metric; so is, with --full, the x @ W GEMM.
 
 N > 1: the graph is sharded by destination range (edge balanced), built from
 per-rank slices of the edge list (ShardedGraph.for_gcn_from_slices: no rank
@@ -41,8 +50,9 @@ pushes a partial row of the destination, whichever covers the cross edges
 with fewer rows); --no-halo-cover pulls every remote source.  value = E' /
 max-over-ranks step time (strong scaling).  extra.per_rank carries each
 rank's halo bytes, the interior / exposed-exchange / boundary split of its
-timed steps, and the same step taken apart after the timed region: the
-exchange alone, the compute alone and the exchange-then-compute step.
+timed steps, and with --full the same step taken apart after the timed
+region: the exchange alone, the compute alone and the exchange-then-compute
+step.
 
 Prints ONE JSON line on rank 0.
 """
@@ -125,9 +135,17 @@ def parse(argv=None):
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="rmat21")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure what the headline figure does not need: the CPU "
+                         "baseline, the reference's device path and the vendor SpMM, the x @ W GEMM, kernel "
+                         "timings in runs of their own and, N>1, the build split, the step taken apart, the "
+                         "compute in turn and the link model")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps write what the last of them computed as DIR/<name>.npy "
+                         "(float32 / float64; a fixed, seeded sample of the rows, N>1: one file per rank)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-ref-paths", action="store_true",
-                    help="skip timing the reference's ATen device path and the vendor SpMM")
+                    help="with --full: skip timing the reference's ATen device path and the vendor SpMM")
     ap.add_argument("--verify", action="store_true",
                     help="after the timed region, hold every output row to |out - ref| <= 1e-5 * max(1, "
                          "sum|w x_j|) against a float64 reference over the rank's own edges")
@@ -147,7 +165,7 @@ def parse(argv=None):
                          "all_to_all_single moves that rank's halo volume as a self split (extra.per_rank[0]"
                          ".rccl_contention: exchange alone, compute alone, overlapped, hidden_frac)")
     ap.add_argument("--no-build-split", action="store_true",
-                    help="N>1: do not take the one-time build apart into device-busy and host time")
+                    help="N>1 with --full: do not take the one-time build apart into device-busy and host time")
     ap.add_argument("--halo-tile", type=int, default=-1,
                     help="N>1: exchange feature tiles of this width (64 / 128 / 256; 256 = whole rows), the "
                          "boundary pass as one launch (see --boundary-per-tile); 0 = the unfused step of "
@@ -319,6 +337,27 @@ def setup_dist(args):
 def barrier(world):
     if world > 1 or dist.is_initialized():
         dist.barrier()
+
+
+DUMP_ROWS = 32768             # rows of an output that --dump-outputs keeps (32 MB of float32 at F = 256)
+DUMP_SEED = 20
+
+
+def dump_outputs(dirname, arrays, rank, world, sharded):
+    """--dump-outputs: each [n, F] array of the last timed step as
+    DIR/<name>.npy (N>1: DIR/<name>_rank<r>.npy, this rank's rows) -- float32,
+    integer arrays as float64 (edge ids are exact there); of more than
+    DUMP_ROWS / world rows a fixed sample, the same rows in every run and for
+    every array (a seeded host permutation, sorted)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        keep = max(1, DUMP_ROWS // max(1, world) // len(arrays))
+        if t.shape[0] > keep:
+            rows = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(DUMP_SEED))[:keep]
+            t = t[rows.sort().values.to(t.device)]
+        t = t.detach().to("cpu", torch.float32 if t.is_floating_point() else torch.float64)
+        np.save(os.path.join(dirname, "%s%s.npy" % (name, "_rank%d" % rank if sharded else "")), t.numpy())
 
 
 def cpu_info():
@@ -618,12 +657,16 @@ def main_gat(args, rank, world, local):
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
             dt = float(tt.item())
         stage(rank, "timed steps done: %.3f ms/step (max over ranks)" % (dt / args.steps * 1e3))
-        # the step's kernel time on this rank (HIP events over back-to-back steps; N > 1:
-        # the exchange alone and the local fused kernels alone, in the same process)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"out": out}, rank, world, sharded)
+        # --full: the step's kernel time on this rank (HIP events over back-to-back steps;
+        # N > 1: the exchange alone and the local fused kernels alone, in the same process)
         reps = max(args.steps, 10)
         split = {}
-        if sharded:
+        kern_ms = None
+        if sharded and (args.full or args.verify):
             xl = mdist.halo_rows(xw, sg.fwd, sg.group)      # pull halo: the verify reference's inputs
+        if args.full and sharded:
             if cover_stats is not None:
                 split = sg.gat_cover.decompose(xw, att, H, C, 0.2, bias, reps, barrier=lambda: barrier(world))
             else:
@@ -641,7 +684,7 @@ def main_gat(args, rank, world, local):
                     torch.cuda.synchronize()
                     split[name] = (time.perf_counter() - t1) / reps * 1e3
             kern_ms = split["compute_only_ms"]
-        else:
+        elif args.full:
             kern_ms = _ev_ms(step, reps)
         verify = None
         if args.verify:
@@ -714,8 +757,9 @@ def main_gat(args, rank, world, local):
             verify = {"all_ranks_within_1e-5_bound": all(r["verify"]["within_1e-5_bound"] for r in ranks),
                       "max_bound_excess": max(r["verify"]["bound_excess"] for r in ranks)}
     cpu = None
-    if rank == 0 and not sharded and not args.no_cpu_baseline:
+    if rank == 0 and not sharded and args.full and not args.no_cpu_baseline:
         cpu = cpu_gat_baseline(ei2, xw, att, H, C, 3_000_000)
+    achieved = comp / (kern_ms * 1e-3) / 1e9 if kern_ms else None     # the kernel's own timing: --full
     if rank == 0:
         line = {
             "metric": "edges aggregated/sec (GATConv 8x32 propagate: fused node scores + leaky_relu + "
@@ -730,8 +774,8 @@ def main_gat(args, rank, world, local):
                        "parallelism": ("dst-range shards x%d, RCCL halo all_to_all (%s)"
                                        % (world, "pull" if args.no_halo_cover else "hybrid cover")) if sharded
                        else "single GPU"},
-            "roofline": {"bound": "hbm", "achieved": comp / (kern_ms * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": comp / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": traffic,
+            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS,
+                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS if achieved else None, "traffic": traffic,
                          "traffic_frac": (traffic / (pmc["kernel_trace_avg_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS)
                          if traffic else None,
                          "traffic_source": traffic_src, "kernel": pmc["kernel"] if pmc else None,
@@ -847,6 +891,8 @@ def main_reddit(args, rank, world, local):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     stage(rank, "timed steps done: %.3f ms/step" % (dt / args.steps * 1e3))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"out": out, "arg": arg}, rank, world, False)
     main_ms = sorted(a.elapsed_time(b) for a, b, _ in ev)
     fix_ms = sorted(b.elapsed_time(c) for _, b, c in ev)
     main_avg, fix_avg = sum(main_ms) / len(main_ms), sum(fix_ms) / len(fix_ms)
@@ -859,7 +905,7 @@ def main_reddit(args, rank, world, local):
     # compulsory: x once, col + eid per slot, rowptr, out and the int64 arg once
     comp = N * F * 4 + E * 8 + (N + 1) * 4 + N * F * 12
     alg = E * (4 * F + 4) + N * (4 * F + 8 * F + 4)       # 1028 B/edge + 3076 B/node
-    cpu = cpu_max_baseline(ei, x, 12_000_000) if not args.no_cpu_baseline else None
+    cpu = cpu_max_baseline(ei, x, 12_000_000) if args.full and not args.no_cpu_baseline else None
     line = {
         "metric": "edges aggregated/sec (aggr='max' + int64 first-index argmax, PyG -10000 mask, F=256)",
         "value": E * args.steps / dt, "unit": "edges/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -1223,7 +1269,7 @@ def main(argv=None):
         local_world = int(os.environ.get("LOCAL_WORLD_SIZE", world))
         crowded = (local_world > 2 * max(1, torch.cuda.device_count())
                    and os.environ.get("GPU_MAX_HW_QUEUES") != "1")
-        meter = BuildMeter(not args.no_build_split and not crowded)
+        meter = BuildMeter(args.full and not args.no_build_split and not crowded)
         sg = meter.run("shards", lambda: mdist.ShardedGraph.for_gcn_from_slices(ei_slice, s0, N, rank, world,
                                                                                chunk=args.chunk or None))
         torch.cuda.synchronize()
@@ -1397,6 +1443,8 @@ def main(argv=None):
     stage(rank, "timed steps done: %d steps, %.3f ms/step (max over ranks)" % (args.steps, dt / args.steps * 1e3))
     ms_per_step = dt / args.steps * 1e3
     value = E2 * args.steps / dt    # whole-job edges aggregated per second
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"out": out_buf}, rank, world, sharded)
 
     # the step once more, outside the timed region, for --verify
     verify = None
@@ -1438,6 +1486,9 @@ def main(argv=None):
         main_ms = sorted(a.elapsed_time(b) for a, b, _ in ev)
         fix_ms = sorted(b.elapsed_time(c) for _, b, c in ev)
         timing_src = "HIP events around each main / fix-up launch inside the timed steps"
+    elif not args.full:
+        main_ms = fix_ms = None
+        timing_src = "N>1: the per-rank kernel rate is timed with --full"
     else:
         # N>1: a step is several launches (per tile, interior + boundary); the
         # per-rank kernel rate is timed on the rank's full local graph instead
@@ -1447,28 +1498,30 @@ def main(argv=None):
     # the kernel the library dispatches for exactly these arguments (no heuristic copy)
     kernel = _lib.kernel_name(st_main, w_csr.data_ptr(), x_src.data_ptr(), x_src.stride(0), F_DIM, "sum",
                               bias.data_ptr(), out_buf.data_ptr(), out_buf.stride(0), dev)
-    main_avg = sum(main_ms) / len(main_ms)
-    fix_avg = sum(fix_ms) / len(fix_ms)
+    main_avg = sum(main_ms) / len(main_ms) if main_ms else None
+    fix_avg = sum(fix_ms) / len(fix_ms) if fix_ms else None
     alg_bytes = E_local * BYTES_PER_EDGE + n_rows * BYTES_PER_NODE
     # compulsory bytes: every input read once and the output written once
     # (x, col, norm, rowptr, out) -- the least any implementation must move,
     # so achieved / peak <= 1 is a true HBM-roofline fraction
     n_src_rows = x_src.shape[0]
     comp_bytes = n_src_rows * F_DIM * 4 + E_local * 8 + (n_rows + 1) * 4 + n_rows * F_DIM * 4
-    achieved = comp_bytes / (main_avg * 1e-3) / 1e9
+    achieved = comp_bytes / (main_avg * 1e-3) / 1e9 if main_avg else None
 
-    # GEMM (reported separately, the only MFMA work)
-    W = torch.randn(F_DIM, F_DIM, device=dev) * 0.06
-    for _ in range(3):
-        torch.matmul(x, W)
-    torch.cuda.synchronize()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(10):
-        torch.matmul(x, W)
-    e1.record()
-    torch.cuda.synchronize()
-    gemm_ms = e0.elapsed_time(e1) / 10
+    # --full: GEMM (reported separately, the only MFMA work)
+    gemm_ms = None
+    if args.full:
+        W = torch.randn(F_DIM, F_DIM, device=dev) * 0.06
+        for _ in range(3):
+            torch.matmul(x, W)
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(10):
+            torch.matmul(x, W)
+        e1.record()
+        torch.cuda.synchronize()
+        gemm_ms = e0.elapsed_time(e1) / 10
 
     # counter traffic (FETCH_SIZE + WRITE_SIZE, corrected) of THIS build's
     # dispatched kernel, from a committed profile summary -- used only when the
@@ -1477,10 +1530,10 @@ def main(argv=None):
     traffic, traffic_src = (None, "N>1: per-rank graphs are not profiled") if sharded else \
         find_pmc(wl["name"], kernel, src_hash)
 
-    # the reference's own device path and a vendor SpMM on the same GPU, same
+    # --full: the reference's own device path and a vendor SpMM on the same GPU, same
     # CSR / weights (outside the timed region; checked against the fused output)
     ref_paths = None
-    if not sharded and not args.no_ref_paths:
+    if not sharded and args.full and not args.no_ref_paths:
         aggregate(x, out=out_buf)
         fused_out = out_buf.clone()
         terms = ops._aggregate(csr, "other", x.abs(), w_csr.abs(), "sum", 0, None)[0]
@@ -1494,7 +1547,7 @@ def main(argv=None):
     # overlap: HIP events on the compute stream around the interior passes,
     # around each tile's work.wait() -- exchange time the compute stream is
     # exposed to -- and around each boundary pass), then the step taken apart:
-    # the exchange alone, the compute alone, exchange-then-compute; gathered to rank 0
+    # the exchange alone, the compute alone, exchange-then-compute (--full); gathered to rank 0
     ranks = None
     if sharded:
         def span(evs, k):
@@ -1524,7 +1577,7 @@ def main(argv=None):
                          "interior_ms": sum(span(e, "interior") for e in step_events) / n,
                          "exchange_exposed_ms": sum(span(e, "wait") for e in step_events) / n,
                          "boundary_ms": sum(span(e, "boundary") for e in step_events) / n})
-        if not args.no_overlap:
+        if args.full and not args.no_overlap:
             form = (x, bufs) if bufs is not None else [x_ov]
             reps_d = max(3, min(args.steps, 10))
             mine["decomposed"] = overlap.decompose(form, out_buf, bias, reps_d, barrier=lambda: barrier(world))
@@ -1558,7 +1611,7 @@ def main(argv=None):
                       "reference": ranks[0]["verify"]["reference"] + ", per rank over its own edges"}
 
     cpu = None
-    if rank == 0 and not sharded and not args.no_cpu_baseline:
+    if rank == 0 and not sharded and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(ei2, norm, x, args.cpu_sample_edges)
         stage(rank, "cpu baseline done")
 
@@ -1581,19 +1634,21 @@ def main(argv=None):
                        "parallelism": "dst-range shards x%d, RCCL halo all_to_all" % world if sharded
                        else "single GPU", "chunk": csr.chunk},
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+                         "frac": achieved / HBM_PEAK_GBS if achieved else None, "traffic": traffic,
                          "traffic_frac": (traffic / (main_avg * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic else None,
                          "traffic_source": traffic_src,
                          "bytes": "achieved = compulsory bytes (x read once, out written once, col + norm + "
                                   "rowptr) / avg launch time",
                          "compulsory_bytes_per_launch": comp_bytes,
                          "algorithmic_bytes_per_launch": alg_bytes,
-                         "algorithmic_GBps_no_cache_credit": alg_bytes / (main_avg * 1e-3) / 1e9,
-                         "kernel": kernel, "source_hash": src_hash,
-                         "avg_launch_ms": main_avg, "median_launch_ms": main_ms[len(main_ms) // 2],
+                         "algorithmic_GBps_no_cache_credit": (alg_bytes / (main_avg * 1e-3) / 1e9) if main_avg
+                         else None,
+                         "kernel": kernel, "source_hash": src_hash, "avg_launch_ms": main_avg,
+                         "median_launch_ms": main_ms[len(main_ms) // 2] if main_ms else None,
                          "fixup_avg_ms": fix_avg, "timing": timing_src},
             "cpu_baseline": cpu,
-            "extra": {"gemm_xW_ms": gemm_ms, "layer_ms_est": gemm_ms + main_avg + fix_avg,
+            "extra": {"gemm_xW_ms": gemm_ms,
+                      "layer_ms_est": gemm_ms + main_avg + fix_avg if gemm_ms and main_avg else None,
                       "one_time_build_s": t_build, "graph_gen_s": t_gen,
                       "edges_local_rank0": E_local, "n_split_rows": csr.n_split,
                       "halo_rows_rank0": ((plan.n_local_src if args.no_overlap else overlap.n_local_src)
@@ -1620,7 +1675,8 @@ def main(argv=None):
                       "gpu_reference_path_ms": ((ref_paths or {}).get("reference_path") or {}).get("ms"),
                       "hipsparse_spmm_ms": ((ref_paths or {}).get("vendor_spmm") or {}).get("ms"),
                       "same_gpu_paths": ref_paths,
-                      "agg_only_GBps_incl_fixup": alg_bytes / ((main_avg + fix_avg) * 1e-3) / 1e9},
+                      "agg_only_GBps_incl_fixup": (alg_bytes / ((main_avg + fix_avg) * 1e-3) / 1e9) if main_avg
+                      else None},
         }
         emit(line)
     stage(rank, "done")

@@ -1032,7 +1032,7 @@ def test_bench_multi_rank_path_end_to_end():
     meaningless, the line's shape, the shard bookkeeping, the per-rank stage
     markers and the step decomposition are what is checked).  --verify holds
     every rank's rows to the float64 bound over its own edges."""
-    d, err = _run_bench(["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+    d, err = _run_bench(["bench.py", "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
                          "--no-ref-paths", "--verify"], {"MP_BENCH_BACKEND": "gloo"})
     assert d["n_gpus"] == 2 and d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0
     assert d["config"]["num_edges"] == 62_094_512 and d["cpu_baseline"] is None
@@ -1122,7 +1122,8 @@ def test_bench_gat_workload(gpus):
     at one GPU and as 2 gloo ranks sharing the device (bench.py's own launch):
     every rank's rows within 1e-5 * max(1, sum|alpha x_j|) of a float64 GATConv
     formula over its own edges; per-rank exchange-only / compute-only times."""
-    args = ["bench.py", "--workload", "gat", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--verify"]
+    args = ["bench.py", "--workload", "gat", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
+            "--verify"]
     if gpus > 1:
         d, _ = _run_bench(args[:1] + ["--gpus", str(gpus)] + args[1:], {"MP_BENCH_BACKEND": "gloo"})
         assert d["extra"]["verify"]["all_ranks_within_1e-5_bound"], d["extra"]["verify"]
@@ -1153,7 +1154,7 @@ def test_bench_sharded_path_over_rccl_one_rank():
     env.pop("MP_BENCH_BACKEND", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "1",
-           "--sharded", "--steps", "3", "--warmup", "1"]
+           "--sharded", "--steps", "3", "--warmup", "1", "--full"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     # the one JSON line alone on stdout: RCCL's version banner goes to stderr

@@ -566,6 +566,36 @@ def test_bench_verify_max_matches_the_serial_loop():
     assert not bench.verify_max(out, bad, x, src, dst)["args_bitwise_equal"]
 
 
+def test_bench_dump_outputs_and_full_option(tmp_path):
+    """bench.py --dump-outputs: every array as DIR/<name>.npy (N>1: one file per
+    rank), float32 (integer arrays float64, exact), at most DUMP_ROWS rows in
+    all -- of a larger output the same seeded rows in every run and for every
+    array of a step; --full is off unless asked for."""
+    import numpy as np
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert not a.full and a.dump_outputs == "" and a.steps == 3
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+    n = bench.DUMP_ROWS + 1001
+    out = torch.arange(n, dtype=torch.float32).view(-1, 1) * torch.ones(1, 3)
+    arg = torch.arange(n, dtype=torch.int64).view(-1, 1) + (1 << 40) * torch.ones(1, 3, dtype=torch.int64)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"out": out, "arg": arg}, 0, 1, False)
+    o, g = np.load(tmp_path / "a" / "out.npy"), np.load(tmp_path / "a" / "arg.npy")
+    assert o.dtype == np.float32 and g.dtype == np.float64
+    assert o.shape == g.shape == (bench.DUMP_ROWS // 2, 3)
+    assert o.nbytes + g.nbytes <= 64 << 20
+    rows = o[:, 0].astype(np.int64)
+    assert (np.diff(rows) > 0).all() and rows.max() < n           # distinct rows of the output, in order
+    assert np.array_equal(g[:, 0], rows + float(1 << 40))          # the same rows, integers exact
+    assert np.array_equal(o, np.load(tmp_path / "b" / "out.npy"))
+    small = torch.randn(5, 4, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "c"), {"out": small}, 1, 2, True)
+    s = np.load(tmp_path / "c" / "out_rank1.npy")
+    assert s.dtype == np.float32 and np.array_equal(s, small.float().numpy())
+
+
 def test_halo_tile_widths():
     """Feature tilings of the sharded step: uniform widths (the last tile takes
     the rest) or an explicit list that must cover F exactly."""

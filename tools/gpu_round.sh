@@ -4,7 +4,7 @@
 # gpurun_out/ (copied into profiles/ as rNN_* when they are kept):
 #   STEPS="tests bench rccl gloo2 gat_gloo2 prof train" R=r05 bash tools/gpu_round.sh
 #   tests     pytest -m gpu                           -> $R_pytest_gpu.txt
-#   bench     python bench.py (the driver's N=1 line)  -> $R_bench_rmat21.json
+#   bench     python bench.py --full (the driver's N=1 line with everything it can carry) -> $R_bench_rmat21.json
 #   bench_gat / bench_products / bench_reddit  the other workloads at N=1 (--verify)
 #   configs   tools/bench_configs.py (configs 3 / 4 / 5, layer steps, Cora graph) -> $R_bench_configs.jsonl
 #   rccl      one RCCL rank, --sharded --emulate-peers 8,4,2 (RCCL beside the aggregation),
@@ -39,24 +39,24 @@ run() {  # name seconds cmd...
 for s in ${STEPS:-tests bench}; do
   case $s in
     tests) run tests 900 bash -c "python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread -p no:cacheprovider > $O/${R}_pytest_gpu.txt 2>&1"; tail -3 $O/${R}_pytest_gpu.txt ;;
-    bench) run bench 400 bash -c "python bench.py > $O/${R}_bench_rmat21.json 2> $O/${R}_bench_rmat21.err"; cut -c1-400 $O/${R}_bench_rmat21.json ;;
-    bench_gat) run bench_gat 400 bash -c "python bench.py --workload gat --verify > $O/${R}_bench_gat_n1.json 2> $O/${R}_bench_gat_n1.err"; cut -c1-300 $O/${R}_bench_gat_n1.json ;;
-    bench_products) run bench_products 500 bash -c "python bench.py --workload products --verify > $O/${R}_bench_products_n1.json 2> $O/${R}_bench_products_n1.err"; cut -c1-300 $O/${R}_bench_products_n1.json ;;
-    bench_reddit) run bench_reddit 500 bash -c "python bench.py --workload reddit --verify > $O/${R}_bench_reddit_n1.json 2> $O/${R}_bench_reddit_n1.err"; cut -c1-300 $O/${R}_bench_reddit_n1.json ;;
+    bench) run bench 400 bash -c "python bench.py --full > $O/${R}_bench_rmat21.json 2> $O/${R}_bench_rmat21.err"; cut -c1-400 $O/${R}_bench_rmat21.json ;;
+    bench_gat) run bench_gat 400 bash -c "python bench.py --full --workload gat --verify > $O/${R}_bench_gat_n1.json 2> $O/${R}_bench_gat_n1.err"; cut -c1-300 $O/${R}_bench_gat_n1.json ;;
+    bench_products) run bench_products 500 bash -c "python bench.py --full --workload products --verify > $O/${R}_bench_products_n1.json 2> $O/${R}_bench_products_n1.err"; cut -c1-300 $O/${R}_bench_products_n1.json ;;
+    bench_reddit) run bench_reddit 500 bash -c "python bench.py --full --workload reddit --verify > $O/${R}_bench_reddit_n1.json 2> $O/${R}_bench_reddit_n1.err"; cut -c1-300 $O/${R}_bench_reddit_n1.json ;;
     configs) run configs 700 bash -c "python tools/bench_configs.py --cpu-baseline > $O/${R}_bench_configs.jsonl 2> $O/${R}_bench_configs.err"; cut -c1-200 $O/${R}_bench_configs.jsonl ;;
-    rccl) run rccl 500 bash -c "python bench.py --sharded --emulate-peers 8,4,2 --steps 10 --warmup 3 --verify > $O/${R}_bench_sharded_rccl_one_rank.json 2> $O/${R}_bench_sharded_rccl_one_rank.err"
+    rccl) run rccl 500 bash -c "python bench.py --full --sharded --emulate-peers 8,4,2 --steps 10 --warmup 3 --verify > $O/${R}_bench_sharded_rccl_one_rank.json 2> $O/${R}_bench_sharded_rccl_one_rank.err"
           run rccl_trace 500 rocprofv3 --kernel-trace --stats -d $O/${R}_rccl_kt -o kt --output-format csv -- python3 bench.py --sharded --emulate-peers 8,4,2 --steps 5 --warmup 2 --no-cpu-baseline --no-ref-paths --no-build-split
           python3 tools/kernel_overlap.py $O/${R}_rccl_kt > $O/${R}_rccl_kernel_overlap.json; cat $O/${R}_rccl_kernel_overlap.json | head -40 ;;
-    rccl_products) run rccl_products 500 bash -c "python bench.py --workload products --sharded --emulate-peers 8,4,2 --steps 10 --warmup 3 --verify > $O/${R}_bench_sharded_rccl_one_rank_products.json 2> $O/${R}_bench_sharded_rccl_one_rank_products.err" ;;
-    gloo2) run gloo2 600 bash -c "MP_BENCH_BACKEND=gloo python bench.py --gpus 2 --steps 3 --warmup 1 --verify > $O/${R}_bench_rmat21_gloo2_rehearsal.json 2> $O/${R}_bench_rmat21_gloo2_rehearsal.err"; cut -c1-300 $O/${R}_bench_rmat21_gloo2_rehearsal.json ;;
-    gloo8) run gloo8 1100 bash -c "GPU_MAX_HW_QUEUES=1 MP_BENCH_BACKEND=gloo python bench.py --gpus 8 --steps 3 --warmup 1 > $O/${R}_bench_rmat21_gloo8_rehearsal.json 2> $O/${R}_bench_rmat21_gloo8_rehearsal.err"; cut -c1-300 $O/${R}_bench_rmat21_gloo8_rehearsal.json ;;
-    gloo4) run gloo4 900 bash -c "GPU_MAX_HW_QUEUES=1 MP_BENCH_BACKEND=gloo python bench.py --gpus 4 --steps 3 --warmup 1 > $O/${R}_bench_rmat21_gloo4_rehearsal.json 2> $O/${R}_bench_rmat21_gloo4_rehearsal.err"; cut -c1-300 $O/${R}_bench_rmat21_gloo4_rehearsal.json ;;
-    products_gloo4) run products_gloo4 1100 bash -c "GPU_MAX_HW_QUEUES=1 MP_BENCH_BACKEND=gloo python bench.py --workload products --gpus 4 --steps 3 --warmup 1 --verify > $O/${R}_bench_products_gloo4_rehearsal.json 2> $O/${R}_bench_products_gloo4_rehearsal.err"; cut -c1-300 $O/${R}_bench_products_gloo4_rehearsal.json ;;
-    products_gloo2) run products_gloo2 900 bash -c "MP_BENCH_BACKEND=gloo python bench.py --workload products --gpus 2 --steps 3 --warmup 1 --verify > $O/${R}_bench_products_gloo2_rehearsal.json 2> $O/${R}_bench_products_gloo2_rehearsal.err"; cut -c1-300 $O/${R}_bench_products_gloo2_rehearsal.json ;;
-    products_gloo8) run products_gloo8 1150 bash -c "GPU_MAX_HW_QUEUES=1 MP_BENCH_BACKEND=gloo python bench.py --workload products --gpus 8 --steps 3 --warmup 1 --verify > $O/${R}_bench_products_gloo8_rehearsal.json 2> $O/${R}_bench_products_gloo8_rehearsal.err"; cut -c1-300 $O/${R}_bench_products_gloo8_rehearsal.json ;;
-    gat_gloo2) run gat_gloo2 600 bash -c "MP_BENCH_BACKEND=gloo python bench.py --gpus 2 --workload gat --steps 3 --warmup 1 --verify > $O/${R}_bench_gat_gloo2_rehearsal.json 2> $O/${R}_bench_gat_gloo2_rehearsal.err"; cut -c1-300 $O/${R}_bench_gat_gloo2_rehearsal.json ;;
-    gat_drop_gloo2) run gat_drop_gloo2 600 bash -c "MP_BENCH_BACKEND=gloo python bench.py --gpus 2 --workload gat --gat-dropout 0.3 --steps 3 --warmup 1 --verify > $O/${R}_bench_gat_dropout_gloo2_rehearsal.json 2> $O/${R}_bench_gat_dropout_gloo2_rehearsal.err"; cut -c1-300 $O/${R}_bench_gat_dropout_gloo2_rehearsal.json ;;
-    gat_drop_gloo4) run gat_drop_gloo4 900 bash -c "GPU_MAX_HW_QUEUES=1 MP_BENCH_BACKEND=gloo python bench.py --gpus 4 --workload gat --gat-dropout 0.3 --steps 3 --warmup 1 --verify > $O/${R}_bench_gat_dropout_gloo4_rehearsal.json 2> $O/${R}_bench_gat_dropout_gloo4_rehearsal.err"; cut -c1-300 $O/${R}_bench_gat_dropout_gloo4_rehearsal.json ;;
+    rccl_products) run rccl_products 500 bash -c "python bench.py --full --workload products --sharded --emulate-peers 8,4,2 --steps 10 --warmup 3 --verify > $O/${R}_bench_sharded_rccl_one_rank_products.json 2> $O/${R}_bench_sharded_rccl_one_rank_products.err" ;;
+    gloo2) run gloo2 600 bash -c "MP_BENCH_BACKEND=gloo python bench.py --full --gpus 2 --steps 3 --warmup 1 --verify > $O/${R}_bench_rmat21_gloo2_rehearsal.json 2> $O/${R}_bench_rmat21_gloo2_rehearsal.err"; cut -c1-300 $O/${R}_bench_rmat21_gloo2_rehearsal.json ;;
+    gloo8) run gloo8 1100 bash -c "GPU_MAX_HW_QUEUES=1 MP_BENCH_BACKEND=gloo python bench.py --full --gpus 8 --steps 3 --warmup 1 > $O/${R}_bench_rmat21_gloo8_rehearsal.json 2> $O/${R}_bench_rmat21_gloo8_rehearsal.err"; cut -c1-300 $O/${R}_bench_rmat21_gloo8_rehearsal.json ;;
+    gloo4) run gloo4 900 bash -c "GPU_MAX_HW_QUEUES=1 MP_BENCH_BACKEND=gloo python bench.py --full --gpus 4 --steps 3 --warmup 1 > $O/${R}_bench_rmat21_gloo4_rehearsal.json 2> $O/${R}_bench_rmat21_gloo4_rehearsal.err"; cut -c1-300 $O/${R}_bench_rmat21_gloo4_rehearsal.json ;;
+    products_gloo4) run products_gloo4 1100 bash -c "GPU_MAX_HW_QUEUES=1 MP_BENCH_BACKEND=gloo python bench.py --full --workload products --gpus 4 --steps 3 --warmup 1 --verify > $O/${R}_bench_products_gloo4_rehearsal.json 2> $O/${R}_bench_products_gloo4_rehearsal.err"; cut -c1-300 $O/${R}_bench_products_gloo4_rehearsal.json ;;
+    products_gloo2) run products_gloo2 900 bash -c "MP_BENCH_BACKEND=gloo python bench.py --full --workload products --gpus 2 --steps 3 --warmup 1 --verify > $O/${R}_bench_products_gloo2_rehearsal.json 2> $O/${R}_bench_products_gloo2_rehearsal.err"; cut -c1-300 $O/${R}_bench_products_gloo2_rehearsal.json ;;
+    products_gloo8) run products_gloo8 1150 bash -c "GPU_MAX_HW_QUEUES=1 MP_BENCH_BACKEND=gloo python bench.py --full --workload products --gpus 8 --steps 3 --warmup 1 --verify > $O/${R}_bench_products_gloo8_rehearsal.json 2> $O/${R}_bench_products_gloo8_rehearsal.err"; cut -c1-300 $O/${R}_bench_products_gloo8_rehearsal.json ;;
+    gat_gloo2) run gat_gloo2 600 bash -c "MP_BENCH_BACKEND=gloo python bench.py --full --gpus 2 --workload gat --steps 3 --warmup 1 --verify > $O/${R}_bench_gat_gloo2_rehearsal.json 2> $O/${R}_bench_gat_gloo2_rehearsal.err"; cut -c1-300 $O/${R}_bench_gat_gloo2_rehearsal.json ;;
+    gat_drop_gloo2) run gat_drop_gloo2 600 bash -c "MP_BENCH_BACKEND=gloo python bench.py --full --gpus 2 --workload gat --gat-dropout 0.3 --steps 3 --warmup 1 --verify > $O/${R}_bench_gat_dropout_gloo2_rehearsal.json 2> $O/${R}_bench_gat_dropout_gloo2_rehearsal.err"; cut -c1-300 $O/${R}_bench_gat_dropout_gloo2_rehearsal.json ;;
+    gat_drop_gloo4) run gat_drop_gloo4 900 bash -c "GPU_MAX_HW_QUEUES=1 MP_BENCH_BACKEND=gloo python bench.py --full --gpus 4 --workload gat --gat-dropout 0.3 --steps 3 --warmup 1 --verify > $O/${R}_bench_gat_dropout_gloo4_rehearsal.json 2> $O/${R}_bench_gat_dropout_gloo4_rehearsal.err"; cut -c1-300 $O/${R}_bench_gat_dropout_gloo4_rehearsal.json ;;
     diag) run diag 500 bash -c "python tools/gat_shard_diag.py > $O/${R}_gat_shard_diag.jsonl 2> $O/${R}_gat_shard_diag.err"; cat $O/${R}_gat_shard_diag.jsonl ;;
     prof) PROF_OUT=$O/${R}_prof run prof 1100 bash tools/profile.sh ;;
     prof_gat) PROF_OUT=$O/${R}_prof_gat NO_CALIB=1 BENCH_ARGS="--workload gat" run prof_gat 1100 bash tools/profile.sh ;;
