@@ -622,6 +622,49 @@ int mp_shard_plan(const int64_t* key, const int64_t* other, int64_t n_edges, int
                   int64_t* edge_pos, int64_t* local_key, int64_t* local_other,
                   int64_t* halo_nodes, int64_t* counts, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- SplineConv: fused B-spline aggregation (csrc/mp_spline.hip) -----------
+ * Per edge e = (j -> i) with pseudo-coordinates u[e, 0..D) in [0, 1] (pseudo
+ * [n_pseudo_edges, D] fp32, ORIGINAL edge order), kernel sizes ks[d], open
+ * flags op[d], degree M, S = (M+1)^D and K = prod ks:
+ *   v_d = u[e,d] * float(ks[d] - M*op[d])  (one fp32 multiply),  f_d = v_d - floor(v_d)
+ *   basis[e,s] = prod_d B_M(f_d, k_d),     k_d = the d-th base-(M+1) digit of s
+ *   wi[e,s]    = sum_d ((floor(v_d) + k_d) mod ks[d]) * prod_{d' < d} ks[d']
+ * B_1 = {1-f, f}; B_2 = {f^2/2 - f + 1/2, -f^2 + f + 1/2, f^2/2};
+ * B_3 = {(1-f)^3/6, (3f^3 - 6f^2 + 4)/6, (-3f^3 + 3f^2 + 3f + 1)/6, f^3/6}.
+ * Replaces torch_spline_conv's SplineBasis + SplineWeighting and the
+ * scatter_add / scatter_mean after them, reordered so that no per-edge basis,
+ * index or message array exists: one segmented pass and one dense GEMM.
+ * kernel_size / is_open are HOST int32[D] arrays (copied into the kernel
+ * arguments).  Limits (mp_spline_ok != 0): 1 <= D <= 3, 1 <= degree <= 3,
+ * ks[d] - degree*op[d] >= 1, K <= 256, F >= 1.  A coordinate outside [0, 1]
+ * wraps modulo ks[d]: no bin or column is ever out of range.
+ * Both aggregate calls walk g->rowptr / col / eid only (col and eid required;
+ * the wave schedule is not read), visit a row's slots in slot order from one
+ * owner and add left to right: deterministic, no atomics.  Rows of any length
+ * are summed serially; hub rows are not split.  n_pseudo_edges must cover the
+ * edge-id space of g (g->n_ids, or g->n_edges when that is 0).
+ *   mp_spline_basis_f32: basis [n_edges, S] fp32 and weight_index [n_edges, S]
+ *     int64 in edge order (basis_bytes / weight_index_bytes: their extents).
+ *   mp_spline_aggregate_bins_f32 (x [n_cols, ldx >= F]):
+ *     out[r, k*F + f] = scale[r] * sum_{slots of r} sum_{s: wi = k} basis * x[col[slot], f]
+ *     ldo >= K*F; all K*F entries of every row are written exactly once
+ *     (zeros for rows without slots).
+ *   mp_spline_aggregate_gather_f32 (x [n_cols, K, F], ldx >= K*F):
+ *     out[r, f] = scale[r] * sum_{slots of r} sum_s basis * x[col[slot], wi*F + f] (+ bias[f])
+ * row_scale [n_rows] or NULL (= 1), bias [F] or NULL. */
+int mp_spline_ok(int32_t D, int32_t degree, const int32_t* kernel_size, const int32_t* is_open, int32_t F);
+int mp_spline_basis_f32(const float* pseudo, int64_t n_edges, int32_t D, const int32_t* kernel_size,
+                        const int32_t* is_open, int32_t degree, float* basis, size_t basis_bytes,
+                        int64_t* weight_index, size_t weight_index_bytes, void* stream);
+int mp_spline_aggregate_bins_f32(const mp_csr* g, const float* pseudo, int64_t n_pseudo_edges, int32_t D,
+                                 const int32_t* kernel_size, const int32_t* is_open, int32_t degree,
+                                 const float* x, int64_t ldx, int32_t F, const float* row_scale,
+                                 float* out, int64_t ldo, void* stream);
+int mp_spline_aggregate_gather_f32(const mp_csr* g, const float* pseudo, int64_t n_pseudo_edges, int32_t D,
+                                   const int32_t* kernel_size, const int32_t* is_open, int32_t degree,
+                                   const float* x, int64_t ldx, int32_t F, const float* row_scale,
+                                   const float* bias, float* out, int64_t ldo, void* stream);
+
 /* ---- other dtypes (csrc/mp_dtype.hip) -------------------------------------
  * torch_scatter 2.0.4 reduces any dtype ([U8/U9]); the fp32 hot path is
  * mp_aggregate_f32, these are the breadth path for the rest. */

@@ -149,6 +149,12 @@ SIGNATURES = {
     "mp_segment_reduce": (ctypes.c_int, [ctypes.POINTER(MpCsr), i32, c_p, i64, i32, i32, i32, c_p, i64, c_p, c_p]),
     "mp_gather_rows_any": (ctypes.c_int, [i32, c_p, i64, c_p, i64, i32, c_p, i64, c_p]),
     "mp_scatter_arg_any": (ctypes.c_int, [i32, c_p, c_p, i64, i32, i64, c_p, i64, c_p]),
+    "mp_spline_ok": (ctypes.c_int, [i32, i32, c_p, c_p, i32]),
+    "mp_spline_basis_f32": (ctypes.c_int, [c_p, i64, i32, c_p, c_p, i32, c_p, sz, c_p, sz, c_p]),
+    "mp_spline_aggregate_bins_f32": (ctypes.c_int, [ctypes.POINTER(MpCsr), c_p, i64, i32, c_p, c_p, i32, c_p, i64,
+                                                    i32, c_p, c_p, i64, c_p]),
+    "mp_spline_aggregate_gather_f32": (ctypes.c_int, [ctypes.POINTER(MpCsr), c_p, i64, i32, c_p, c_p, i32, c_p, i64,
+                                                      i32, c_p, c_p, c_p, i64, c_p]),
 }
 
 _lib = None

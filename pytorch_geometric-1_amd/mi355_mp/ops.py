@@ -1302,3 +1302,209 @@ def feature_transform(x, w, row_exact=False):
     if not w.requires_grad:
         return torch.matmul(x, w)
     return _FeatureTransform.apply(x, w)
+
+
+# ---------------------------------------------------------------------------
+# SplineConv: fused B-spline aggregation (csrc/mp_spline.hip)
+# ---------------------------------------------------------------------------
+
+def _int_list(v):
+    if torch.is_tensor(v):
+        v = v.reshape(-1).tolist()
+    elif isinstance(v, (int, bool)):
+        v = [v]
+    return [int(a) for a in v]
+
+
+def _spline_geom(kernel_size, is_open_spline, degree, D, F=1):
+    """(ks int32[D], open int32[D], K, S) as the C-ABI takes them (host arrays).
+    The limits of the fused path live in one place, mp_spline_ok; a shape it
+    refuses raises NotImplementedError with its text, which names the limit."""
+    ks = _int_list(kernel_size)
+    op = [int(bool(a)) for a in _int_list(is_open_spline)]
+    D, degree = int(D), int(degree)
+    if len(ks) != D or len(op) != D:
+        raise ValueError("mi355_mp: pseudo has %d dimensions, kernel_size %d and is_open_spline %d entries"
+                         % (D, len(ks), len(op)))
+    ks_a = (_lib.i32 * max(D, 1))(*ks)
+    op_a = (_lib.i32 * max(D, 1))(*op)
+    lib = _lib.load()
+    if not lib.mp_spline_ok(D, degree, ks_a, op_a, max(int(F), 1)):
+        raise NotImplementedError("mi355_mp: outside the fused spline path's limits: "
+                                  + lib.mp_last_error().decode(errors="replace"))
+    K = 1
+    for k in ks:
+        K *= k
+    return ks_a, op_a, K, (degree + 1) ** D
+
+
+def _spline_pseudo(pseudo):
+    if pseudo.dtype != torch.float32:
+        raise TypeError("mi355_mp: pseudo must be float32 (got %s)" % pseudo.dtype)
+    if pseudo.dim() == 1:
+        pseudo = pseudo.unsqueeze(-1)
+    if pseudo.dim() != 2:
+        raise ValueError("mi355_mp: pseudo must be [edges, dimensions]")
+    return pseudo.contiguous()
+
+
+def spline_basis(pseudo, kernel_size, is_open_spline, degree):
+    """(basis [E, S] fp32, weight_index [E, S] int64) of the B-spline basis in
+    edge order (mp_spline_basis_f32; torch_spline_conv's SplineBasis)."""
+    _lib.require_device(pseudo)
+    pseudo = _spline_pseudo(pseudo)
+    E, D = pseudo.shape
+    ks_a, op_a, _K, S = _spline_geom(kernel_size, is_open_spline, degree, D)
+    basis = torch.empty((E, S), dtype=torch.float32, device=pseudo.device)
+    wi = torch.empty((E, S), dtype=torch.int64, device=pseudo.device)
+    _lib.check(_lib.load().mp_spline_basis_f32(pseudo.data_ptr(), E, D, ks_a, op_a, int(degree), basis.data_ptr(),
+                                               _lib.nbytes(basis), wi.data_ptr(), _lib.nbytes(wi),
+                                               _lib.stream_ptr(pseudo.device)), "mp_spline_basis_f32")
+    return basis, wi
+
+
+def spline_bins(csr, pseudo, geom, degree, x, row_scale=None):
+    """out[r, k*F + f] = scale[r] * sum over the slots of r and s with wi = k of
+    basis * x[col[slot], f] (mp_spline_aggregate_bins_f32); geom from
+    _spline_geom.  No autograd."""
+    ks_a, op_a, K, _S = geom
+    F = x.shape[1]
+    out = torch.empty((csr.n_rows, K * F), dtype=torch.float32, device=x.device)
+    if csr.n_rows and F:
+        _lib.check(_lib.load().mp_spline_aggregate_bins_f32(
+            csr.struct("other"), pseudo.data_ptr(), pseudo.shape[0], pseudo.shape[1], ks_a, op_a, int(degree),
+            x.data_ptr(), x.stride(0), F, _lib.ptr(row_scale), out.data_ptr(), out.stride(0),
+            _lib.stream_ptr(x.device)), "mp_spline_aggregate_bins_f32")
+    return out
+
+
+def spline_gather(csr, pseudo, geom, degree, xk, F, row_scale=None, bias=None):
+    """out[r, f] = scale[r] * sum over the slots of r and s of
+    basis * xk[col[slot], wi*F + f] (+ bias) (mp_spline_aggregate_gather_f32);
+    xk [n_cols, K*F].  No autograd."""
+    ks_a, op_a, K, _S = geom
+    out = torch.empty((csr.n_rows, F), dtype=torch.float32, device=xk.device)
+    if csr.n_rows and F:
+        _lib.check(_lib.load().mp_spline_aggregate_gather_f32(
+            csr.struct("other"), pseudo.data_ptr(), pseudo.shape[0], pseudo.shape[1], ks_a, op_a, int(degree),
+            xk.data_ptr(), xk.stride(0), F, _lib.ptr(row_scale), _lib.ptr(bias), out.data_ptr(), out.stride(0),
+            _lib.stream_ptr(xk.device)), "mp_spline_aggregate_gather_f32")
+    return out
+
+
+# bins kernels above this many kernels hold fewer than 4 waves per 64 KiB workgroup
+SPLINE_BINS_FULL_BLOCK = 64
+
+
+def spline_form(S, f_in, f_out, K=1):
+    """The forward's form, as measured (tools/bench_spline.py,
+    profiles/spline_conv_bench*.json).  By gathered floats per edge
+    the rule would be transform first ('gather': S * Fout floats of x W per
+    edge) when S * Fout < Fin, else aggregate first ('bins': Fin floats of x
+    per edge); where that rule picks gather (Cora's 1433 -> 16 and 16 -> 7
+    with S = 2) gather was never ahead -- the shapes are host-bound and the
+    forms differ by less than the spread -- so it is not used.  Gather won at
+    one measured shape: the mesh layer 64 -> 64 with K = 125, S = 8, where the
+    bins kernel is bound by its LDS (K > 64: at most 2 waves per workgroup)
+    and writes K * Fin floats per row.  So: gather when K > 64, Fin >= 64 and
+    S * Fout <= 8 * Fin; bins otherwise.  A record of the measured shapes, not
+    a model: bins keeps A [N, K * Fin] for the backward, and with a wide Fin a
+    caller short of memory should force form='gather'."""
+    if K > SPLINE_BINS_FULL_BLOCK and f_in >= 64 and S * f_out <= 8 * f_in:
+        return "gather"
+    return "bins"
+
+
+class _SplinePropagate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, graph, pseudo, geom, degree, reduce, form):
+        K, S = geom[2], geom[3]
+        f_in, f_out = weight.shape[1], weight.shape[2]
+        csr = graph.dst
+        scale = None
+        if reduce == "mean":
+            scale = (1.0 / csr.degree().clamp(min=1).to(torch.float32)).contiguous()
+        A = None
+        if form == "bins":
+            A = spline_bins(csr, pseudo, geom, degree, x, scale)
+            wf = weight.reshape(K * f_in, f_out)
+            out = torch.matmul(A, wf) if bias is None else torch.addmm(bias, A, wf)
+        else:
+            xw = torch.matmul(x, weight.permute(1, 0, 2).reshape(f_in, K * f_out))
+            out = spline_gather(csr, pseudo, geom, degree, xw, f_out, scale, bias)
+        ctx.graph, ctx.geom, ctx.degree = graph, geom, degree
+        ctx.has_bias = bias is not None
+        # the cached Graph holds its edge_index weakly and builds the transposed CSR
+        # on first use, in backward: keep the tensor alive until then
+        ctx.save_for_backward(x, weight, pseudo, scale, A if ctx.needs_input_grad[1] else None,
+                              graph._edge_index())
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, weight, pseudo, scale, A, _edge_index = ctx.saved_tensors
+        graph, geom, degree = ctx.graph, ctx.geom, ctx.degree
+        K, S = geom[2], geom[3]
+        f_in, f_out = weight.shape[1], weight.shape[2]
+        g = g.contiguous()
+        gx = gw = gb = None
+        if ctx.has_bias and ctx.needs_input_grad[2]:
+            gb = col_sums(g)
+        gs = g if scale is None else g * scale.view(-1, 1)
+        want_x, want_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        # the transposed pass: rows = source nodes, gathers destination rows of g
+        x_by_gather = want_x and S * f_in < f_out
+        B = None
+        if (want_x and not x_by_gather) or (want_w and A is None):
+            B = spline_bins(graph.src, pseudo, geom, degree, gs)            # [n_src, K * Fout]
+        if want_x:
+            if x_by_gather:
+                gk = torch.matmul(gs, weight.reshape(K * f_in, f_out).t())  # [n_dst, K * Fin]
+                gx = spline_gather(graph.src, pseudo, geom, degree, gk, f_in)
+            else:
+                gx = torch.matmul(B, weight.permute(0, 2, 1).reshape(K * f_out, f_in))
+        if want_w:
+            if A is not None:
+                gw = torch.matmul(A.t(), g).view(K, f_in, f_out)            # A carries the row scale
+            else:
+                gw = torch.matmul(x.t(), B).view(f_in, K, f_out).permute(1, 0, 2).contiguous()
+        return gx, gw, gb, None, None, None, None, None, None
+
+
+def spline_propagate(graph, x, weight, pseudo, kernel_size, is_open_spline, degree, reduce="mean", form=None,
+                     bias=None):
+    """out[i] = AGGR_{e = (j -> i)} sum_s basis[e, s] * x[j] @ weight[wi[e, s]] (+ bias)
+
+    SplineConv's propagate (torch_spline_conv's SplineBasis + SplineWeighting,
+    then scatter_add / scatter_mean) as one segmented pass and one dense GEMM;
+    weight [K, Fin, Fout], pseudo [E, D] in [0, 1] in edge order.  reduce 'add'
+    or 'mean' (mean divides by max(deg, 1)); form None picks by spline_form,
+    'bins' / 'gather' force one.  Deterministic, native forward and backward
+    (the same two kernels over the transposed CSR); no gradient for pseudo."""
+    if reduce == "max":
+        raise NotImplementedError("mi355_mp: spline_propagate has no aggr='max' (add and mean only)")
+    if reduce not in ("add", "sum", "mean"):
+        raise ValueError("unknown reduce %r" % (reduce,))
+    if form not in (None, "bins", "gather"):
+        raise ValueError("unknown form %r" % (form,))
+    if pseudo.requires_grad:
+        raise NotImplementedError("mi355_mp: spline_propagate has no gradient with respect to pseudo")
+    _lib.require_device(x, weight, pseudo, bias)
+    x = _f32_2d(x, "x")
+    if x.stride(0) < max(x.shape[1], 1):
+        x = x.contiguous()
+    pseudo = _spline_pseudo(pseudo)
+    if weight.dtype != torch.float32 or weight.dim() != 3 or weight.shape[1] != x.shape[1]:
+        raise ValueError("mi355_mp: weight must be float32 [K, %d, Fout] (got %s %s)"
+                         % (x.shape[1], weight.dtype, tuple(weight.shape)))
+    geom = _spline_geom(kernel_size, is_open_spline, degree, pseudo.shape[1], max(x.shape[1], weight.shape[2]))
+    if weight.shape[0] != geom[2]:
+        raise ValueError("mi355_mp: weight holds %d kernels, prod(kernel_size) = %d" % (weight.shape[0], geom[2]))
+    if pseudo.shape[0] != graph.dst.n_edges:
+        raise ValueError("mi355_mp: pseudo has %d rows, the graph %d edges" % (pseudo.shape[0], graph.dst.n_edges))
+    if x.shape[0] != graph.n_src:
+        raise ValueError("mi355_mp: x has %d rows, the graph %d source nodes" % (x.shape[0], graph.n_src))
+    if form is None:
+        form = spline_form(geom[3], weight.shape[1], weight.shape[2], geom[2])
+    reduce = "add" if reduce == "sum" else reduce
+    return _SplinePropagate.apply(x, weight, bias, graph, pseudo, geom, int(degree), reduce, form)

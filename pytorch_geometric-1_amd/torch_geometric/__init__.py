@@ -13,6 +13,7 @@ from .debug import is_debug_enabled, debug, set_debug  # noqa: F401
 from . import utils  # noqa: F401
 from . import data  # noqa: F401
 from . import nn  # noqa: F401
+from . import transforms  # noqa: F401
 
 __version__ = "1.4.3"
 

@@ -7,5 +7,7 @@ from .cheb_conv import ChebConv
 from .agnn_conv import AGNNConv
 from .sg_conv import SGConv
 from .gin_conv import GINConv
+from .spline_conv import SplineConv
 
-__all__ = ["MessagePassing", "GCNConv", "GATConv", "SAGEConv", "GraphConv", "ChebConv", "AGNNConv", "SGConv", "GINConv"]
+__all__ = ["MessagePassing", "GCNConv", "GATConv", "SAGEConv", "GraphConv", "ChebConv", "AGNNConv", "SGConv", "GINConv",
+           "SplineConv"]
