@@ -103,8 +103,16 @@ def test_kernels_against_float64(edges, graph, F, K):
 # the instantiations the grid above does not launch: degree 3 at D = 3 (the widest
 # bins / gather kernels), and kernel sizes <= degree at D > 1 (bins repeat within
 # a slot: the serial read-modify-write path)
+#
+# and the block shapes of the bins kernel that K alone selects (waves = min(4,
+# 65536 / (256 K))): three waves (K in 65..85), one wave (K in 129..256), and
+# K = 256, whose 65536 bytes of dynamic LDS are the launch limit; F = 130 there
+# has two feature tiles and a third with a two-lane tail
 @pytest.mark.parametrize("ks,op,M,F", [([5, 5, 5], [1, 1, 0], 3, 1), ([3, 2], [0, 0], 2, 5),
-                                       ([4, 3, 2], [0, 0, 0], 2, 33), ([3, 3, 3], [0, 0, 0], 3, 5)])
+                                       ([4, 3, 2], [0, 0, 0], 2, 33), ([3, 3, 3], [0, 0, 0], 3, 5),
+                                       ([9, 8], [1, 0], 2, 5), ([4, 4, 5], [0, 1, 0], 1, 33),
+                                       ([16, 16], [1, 1], 3, 5), ([256], [1], 1, 1), ([256], [0], 3, 64),
+                                       ([8, 8, 4], [1, 0, 1], 2, 130), ([13, 10], [0, 0], 1, 1)])
 def test_kernels_other_instantiations(edges, graph, ks, op, M, F):
     _check_kernels(edges, graph, ks, op, M, F, math.prod(ks))
 
@@ -275,6 +283,25 @@ def test_bins_bit_exact_on_dyadic_inputs(edges, graph):
     A = ops.spline_bins(graph.dst, u.to(DEV), geom, M, x.to(DEV))
     rb, rwi = R.basis(u, ks, op, M)
     ref = R.bins(edges[1], edges[0], N, rb, rwi, 25, x)
+    assert torch.equal(A.cpu().double(), ref)
+
+
+def test_bins_bit_exact_at_the_lds_limit(edges, graph):
+    """The same at K = 256 ([16, 16], the one-wave block with 65536 bytes of
+    dynamic LDS): open splines, so v = u * 15 is a multiple of 1/8 below 16,
+    exact in fp32, as are the degree-1 basis values (multiples of 1/8), their
+    products (of 1/64) with |x| <= 4 and every partial sum of a row's 700
+    slots; the bins reach index 255.  A bin-addressing error shows without a
+    tolerance."""
+    from mi355_mp import ops
+    ks, op, M, F = [16, 16], [1, 1], 1, 7
+    u, x = _exact_inputs(edges, F)
+    geom = ops._spline_geom(ks, op, M, 2, F)
+    assert geom[2] == 256
+    A = ops.spline_bins(graph.dst, u.to(DEV), geom, M, x.to(DEV))
+    rb, rwi = R.basis(u, ks, op, M)
+    assert int(rwi.max()) == 255 and int(rwi.min()) == 0
+    ref = R.bins(edges[1], edges[0], N, rb, rwi, 256, x)
     assert torch.equal(A.cpu().double(), ref)
 
 
