@@ -111,7 +111,7 @@ def gcn_conv(x, edge_index, weight, bias=None, edge_weight=None, improved=False)
 # --- GATConv [U6] -----------------------------------------------------------
 
 def gat_dropout_keep_slots(seed, p, H, n_slots, start=0):
-    """The fused kernels' attention-dropout keep mask (csrc/mp_aggregate.hip
+    """The fused kernels' attention-dropout keep mask (csrc/mp_agg.h
     drop_hash / drop_bits), restated in numpy: bool [n_slots, H], slot s of the
     destination CSR (s from `start`), head h kept iff hash(seed, s*H + h) >= floor(p * 2^32).
     The reference draws its mask from torch's RNG (GATConv.message:

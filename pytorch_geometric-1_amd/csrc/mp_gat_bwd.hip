@@ -4,7 +4,9 @@
 // The alpha-weighted transposed aggregation is mp_aggregate_heads_f32 (the
 // main kernel template with a per-head weight).  Reference: GATConv.message
 // + utils.softmax autograd (PyG 1.4.3 [U3,U6]).
-#include "mp_common.h"
+// The fused backward (mp_gat_backward*_f32) is GatBwdRed on the merge-path
+// engine of mp_agg.h, over the transposed CSR.
+#include "mp_agg.h"
 
 namespace mp {
 
@@ -340,6 +342,134 @@ __global__ void k_heads_outer_add(float* __restrict__ y, int64_t ldy, const floa
   store_frag<VEC>(d, v);
 }
 
+// GATConv backward in one pass over the TRANSPOSED CSR (row j = source node,
+// slots = its out-edges j->i in original edge order).  Per slot the gathered
+// row is g_i = d out_i, and with alpha_ij rebuilt from the forward's row
+// statistics (m_i, 1/(s_i + 1e-16)):
+//   d xw_j    += alpha_ij g_i                               (message part)
+//   dalpha_ij  = <g_i, xw_j>_h                              (the row's own xw)
+//   de_ij      = alpha_ij (dalpha_ij - rs_i) leaky'(score)  (softmax + leaky_relu backward)
+//   d a_src_j += de_ij,  and at the row end d xw_j += d a_src_j (x) att_src.
+// rs_i = <g_i, agg_i>_h replaces the per-edge sum_j alpha_ij dalpha_ij, so no
+// [E, H*C] product is ever formed.  The destination's (a_dst, m, 1/den, rs)
+// come packed in one float4 per (node, head): one 16-byte gather per slot.
+// A head spans HL = C/VEC lanes (power of two); its dot product is reduced
+// with DPP adds inside the head group.  Gradients are checked to a
+// tolerance, so this pass uses FMA and the hardware exp.
+template <int VEC, bool DR = false>
+struct GatBwdRed : RedFlags {
+  static constexpr bool kEid = true;
+  static constexpr bool kGatB = true;
+  static constexpr bool kDrop = DR;
+  static constexpr bool kStat = true;
+  struct Part {
+    float v[VEC];
+    float d;
+  };
+  float acc[VEC];
+  float y[VEC];
+  float dacc, as;
+  float gd = 0.f;  // d a_dst of the row (ga_dst_in)
+  int h, hl;
+  bool leader;
+
+  __device__ GatBwdRed(const AggArgs& p, int f, bool act)
+      : h(act ? f / p.C : 0), hl(p.C / VEC), leader(act && ((f / VEC) & (p.C / VEC - 1)) == 0) {}
+
+  __device__ __forceinline__ void begin(const AggArgs& p, int64_t row, bool, int f, bool act) {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
+    dacc = 0.f;
+    Frag<VEC> o = load_frag<VEC>(p.y + row * p.ldy + (act ? f : 0));
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) y[k] = act ? o.v[k] : 0.f;
+    as = p.a_src[row * p.H + h];
+    row_terms(p, row);
+  }
+  // the row's node-wise terms needed at finish (the fix-up, which finishes a
+  // split row without a begin, calls this itself)
+  __device__ __forceinline__ void row_terms(const AggArgs& p, int64_t row) {
+    if (p.ga_dst_in) gd = p.ga_dst_in[row * p.H + h];
+  }
+  // head-group dot product <v, y> (all lanes of the head get the sum)
+  __device__ __forceinline__ float dot(const Frag<VEC>& v) const {
+    float t = v.v[0] * y[0];
+#pragma unroll
+    for (int k = 1; k < VEC; ++k) t = __builtin_fmaf(v.v[k], y[k], t);
+    return group_sum(t, hl);
+  }
+  // DR: the message used alpha * keep / (1 - p), so d xw_j takes that weight and
+  // d alpha = keep / (1 - p) <g_i, xw_j>
+  __device__ __forceinline__ void consume_gatb(const AggArgs& p, const Frag<VEC>& v, float dal, f32x4 q,
+                                               int64_t slot, [[maybe_unused]] uint32_t dbits = 0) {
+    const float sc = as + q.x;
+    const float lk = sc > 0.f ? 1.f : p.slope;
+    const float alpha = __expf(sc * lk - q.y) * q.z;
+    float aw = alpha;
+    if constexpr (DR) {
+      const float dsc = drop_factor(p, dbits, h);
+      aw = alpha * dsc;
+      dal = dal * dsc;
+    }
+    // a one-hot softmax row (1/den == 1 and this edge's alpha == 1: a single edge, or the others
+    // below 2^-24 of it) has d score = alpha (d alpha - rs) = 0 up to those others' weight; the
+    // reference's autograd cancels the identical value there, rs = <g_i, agg_i> would leave the
+    // rounding of two different evaluations -- so the term is 0, as the reference's
+    const float de = (q.z == 1.f && alpha == 1.f) ? 0.f : alpha * (dal - q.w) * lk;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) acc[k] = __builtin_fmaf(aw, v.v[k], acc[k]);
+    dacc += de;
+    if (leader && p.de) p.de[slot * p.H + h] = de;  // no de: the training forward made d a_dst node-wise
+  }
+  __device__ __forceinline__ void consume(const Frag<VEC>&, float, int, float) {}
+  __device__ __forceinline__ void save(PRef r, bool stat_writer) const {
+    Frag<VEC> o;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) o.v[k] = acc[k];
+    store_frag<VEC>(r.v, o);
+    if (stat_writer) r.st[0] = dacc;
+  }
+  static __device__ __forceinline__ Part load(PRef r) {
+    Frag<VEC> o = load_frag<VEC>(r.v);
+    Part q;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) q.v[k] = o.v[k];
+    q.d = r.st[0];
+    return q;
+  }
+  __device__ __forceinline__ void set(const Part& q) {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) acc[k] = q.v[k];
+    dacc = q.d;
+  }
+  __device__ __forceinline__ void merge(const Part& q) {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) acc[k] += q.v[k];
+    dacc += q.d;
+  }
+  __device__ __forceinline__ Part part() const {
+    Part q;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) q.v[k] = acc[k];
+    q.d = dacc;
+    return q;
+  }
+  __device__ __forceinline__ void finish(const AggArgs& p, int64_t row, int64_t, int f, bool act, bool with_bias = true) {
+    if (!act) return;
+    const float* at = p.att + (int64_t)h * 2 * p.C + p.C + (f % p.C);
+    Frag<VEC> o;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) o.v[k] = __builtin_fmaf(dacc, at[k], acc[k]);
+    if (p.ga_dst_in) {  // the x_i use of xw in the score: + d a_dst (x) att_dst
+      const float* ad = p.att + (int64_t)h * 2 * p.C + (f % p.C);
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) o.v[k] = __builtin_fmaf(gd, ad[k], o.v[k]);
+    }
+    store_out<VEC>(p.out + row * p.ldo + f, o);
+    if (leader) p.ga[row * p.H + h] = dacc;
+  }
+};
+
 }  // namespace mp
 
 using namespace mp;
@@ -513,6 +643,109 @@ int mp_heads_outer_add_f32(float* y, int64_t ldy, const float* s, int64_t n, int
   }
   MP_CHECK_LAUNCH();
   return MP_OK;
+}
+
+static int gat_backward(const mp_csr* gt, const float* grad_out, int64_t ldg, const float* xw, const float* a_src,
+                        const float* pack, const float* att, int32_t H, int32_t C, float slope, float* grad_xw,
+                        float* grad_a_src, float* de, const float* ga_dst_in, void* slab, size_t slab_bytes,
+                        int32_t stages, void* stream, uint64_t drop_seed = 0, float p_drop = 0.f,
+                        const int32_t* drop_ids = nullptr) {
+  MP_DEVICE_GUARD(stream);
+  int rc = check_graph(gt, "mp_gat_backward_f32");
+  if (rc) return rc;
+  MP_CHECK_ARG(H > 0 && C > 0, "mp_gat_backward_f32: H, C must be positive");
+  MP_CHECK_ARG(grad_out && xw && a_src && pack && att && grad_xw && grad_a_src,
+               "mp_gat_backward_f32: null pointer");
+  MP_CHECK_ARG((uintptr_t)pack % 16 == 0, "mp_gat_backward_f32: pack must be 16-byte aligned");
+  const int F = H * C;
+  MP_CHECK_ARG(ldg >= F, "mp_gat_backward_f32: ldg < H*C");
+  MP_CHECK_ARG(slab && slab_bytes >= mp_gat_slab_bytes(gt, H, C), "mp_gat_backward_f32: slab workspace too small");
+  AggArgs a{};
+  fill_graph(a, gt);
+  a.F = F;
+  a.x = grad_out;
+  a.ldx = ldg;
+  a.out = grad_xw;
+  a.ldo = F;
+  a.y = xw;
+  a.ldy = F;
+  a.a_src = a_src;
+  a.pack = reinterpret_cast<const f32x4*>(pack);
+  a.att = att;
+  a.de = de;
+  a.ga = grad_a_src;
+  a.ga_dst_in = ga_dst_in;
+  a.H = H;
+  a.C = C;
+  a.slope = slope;
+  carve_slabs(a, slab, kSlabStat);
+  hipStream_t s = as_stream(stream);
+  auto pow2 = [](int q) { return q >= 1 && q <= 64 && (q & (q - 1)) == 0; };
+  const bool v4 = C % 4 == 0 && pow2(C / 4) && (uintptr_t)grad_out % 16 == 0 && ldg % 4 == 0 &&
+                  (uintptr_t)xw % 16 == 0 && (uintptr_t)grad_xw % 16 == 0;
+  // narrower feature tiles for the transposed pass (MP_TUNE_GAT_BWD_VEC 2 / 1: 128- / 64-feature
+  // tiles, XCD-affine like the flat kernel's; a head stays inside one tile)
+  const int bv = (int)tuned_gat_bwd_vec();
+  if (v4 && bv < 4 && F >= 64 * bv * 2 && pow2(C / bv) && (64 * bv) % C == 0) {
+    if (bv == 2) {
+      if (p_drop > 0.f) {
+        set_drop(a, drop_seed, p_drop, drop_ids);
+        return launch<GatBwdRed<2, true>, 2>(a, stages, s);
+      }
+      return launch<GatBwdRed<2>, 2>(a, stages, s);
+    }
+    if (p_drop > 0.f) {
+      set_drop(a, drop_seed, p_drop, drop_ids);
+      return launch<GatBwdRed<1, true>, 1>(a, stages, s);
+    }
+    return launch<GatBwdRed<1>, 1>(a, stages, s);
+  }
+  if (v4) {
+    int lanes = F >= 256 ? kGatLanes : pick_shape(F, ldg, grad_out, F, grad_xw).lanes;
+    if (lanes < C / 4) lanes = C / 4;
+    if (p_drop > 0.f) {
+      set_drop(a, drop_seed, p_drop, drop_ids);
+      return launch<GatBwdRed<4, true>, 4>(a, stages, s, lanes);
+    }
+    return launch<GatBwdRed<4>, 4>(a, stages, s, lanes);
+  }
+  MP_CHECK_ARG(p_drop <= 0.f, "mp_gat_backward_train_drop_f32: needs C/4 a power of two <= 64, 16-byte aligned rows");
+  MP_CHECK_ARG(pow2(C), "mp_gat_backward_f32: C=%d needs C/4 or C to be a power of two <= 64", C);
+  return launch<GatBwdRed<1>, 1>(a, stages, s);
+}
+
+int mp_gat_backward_f32(const mp_csr* gt, const float* grad_out, int64_t ldg, const float* xw, const float* a_src,
+                        const float* pack, const float* att, int32_t H, int32_t C, float slope, float* grad_xw,
+                        float* grad_a_src, float* de, size_t de_bytes, void* slab, size_t slab_bytes, int32_t stages,
+                        void* stream) {
+  // without the training forward's node-wise d a_dst the per-edge d score is the
+  // only way d a_dst comes out: it is required (mp_gat_backward_train_f32 otherwise)
+  MP_CHECK_ARG(de != nullptr || !gt || gt->n_edges == 0,
+               "mp_gat_backward_f32: de is required (use mp_gat_backward_train_f32 after the training forward)");
+  if (gt && H > 0) MP_CHECK_EXTENT("mp_gat_backward_f32", "de", de_bytes, (size_t)gt->n_edges * H * 4);
+  return gat_backward(gt, grad_out, ldg, xw, a_src, pack, att, H, C, slope, grad_xw, grad_a_src, de, nullptr, slab,
+                      slab_bytes, stages, stream);
+}
+
+int mp_gat_backward_train_f32(const mp_csr* gt, const float* grad_out, int64_t ldg, const float* xw,
+                              const float* a_src, const float* pack, const float* att, int32_t H, int32_t C,
+                              float slope, const float* grad_a_dst, float* grad_xw, float* grad_a_src, void* slab,
+                              size_t slab_bytes, int32_t stages, void* stream) {
+  MP_CHECK_ARG(grad_a_dst != nullptr, "mp_gat_backward_train_f32: null grad_a_dst");
+  return gat_backward(gt, grad_out, ldg, xw, a_src, pack, att, H, C, slope, grad_xw, grad_a_src, nullptr,
+                      grad_a_dst, slab, slab_bytes, stages, stream);
+}
+
+int mp_gat_backward_train_drop_f32(const mp_csr* gt, const float* grad_out, int64_t ldg, const float* xw,
+                                   const float* a_src, const float* pack, const float* att, int32_t H, int32_t C,
+                                   float slope, const float* grad_a_dst, uint64_t seed, float p_drop,
+                                   const int32_t* drop_ids, float* grad_xw, float* grad_a_src, void* slab,
+                                   size_t slab_bytes, int32_t stages, void* stream) {
+  int rc = drop_check(p_drop, H, "mp_gat_backward_train_drop_f32");
+  if (rc) return rc;
+  MP_CHECK_ARG(grad_a_dst != nullptr, "mp_gat_backward_train_drop_f32: null grad_a_dst");
+  return gat_backward(gt, grad_out, ldg, xw, a_src, pack, att, H, C, slope, grad_xw, grad_a_src, nullptr,
+                      grad_a_dst, slab, slab_bytes, stages, stream, seed, p_drop, drop_ids);
 }
 
 }  // extern "C"

@@ -3,12 +3,12 @@
 // the reference's own GAT stacks use (ConvexPruning.py:209-214: heads = 1,
 // out_channels drawn at random by ContractionLayerCoefficients, :106-114).
 // The per-head dot products are taken per node here, so the edge passes
-// (GatRed non-own forward, GatBwdWideRed backward in mp_aggregate.hip) need no
-// cross-lane reduction per slot.  One wave per node; a head is walked in
-// 256-feature chunks (lane = 4 features), each lane keeps its running partial
-// across the chunks (separately rounded, chunk order), then one 64-lane
-// shuffle-xor tree (group_sum) per head.
-#include "mp_common.h"
+// (GatRed non-own forward in mp_gat_fwd.hip, GatBwdWideRed backward below, on
+// the engine of mp_agg.h) need no cross-lane reduction per slot.  One wave per
+// node; a head is walked in 256-feature chunks (lane = 4 features), each lane
+// keeps its running partial across the chunks (separately rounded, chunk
+// order), then one 64-lane shuffle-xor tree (group_sum) per head.
+#include "mp_agg.h"
 
 namespace mp {
 
@@ -133,6 +133,121 @@ static unsigned wide_blocks(int64_t n) {
 
 static bool al16(const void* p) { return (uintptr_t)p % 16 == 0; }
 
+// GATConv backward for heads of any width (C % 4 == 0; a head may span several
+// feature tiles, so no per-slot dot product is possible): over the TRANSPOSED
+// CSR (row j = source), with alpha_ij rebuilt from the destination's pack
+// (a_dst, m, 1/den, rs) and the row's own a_src[j,h], lk = leaky'(score):
+//   acc_j  += alpha d g_i              (message part of d xw_j; d = dropout factor)
+//   acc2_j += lk alpha d g_i
+//   sc_j   += lk alpha rs_i            (per head)
+// The per-edge d score never forms: d a_src_j = sum_i lk alpha (d <g_i, xw_j> - rs_i)
+// = <acc2_j, xw_j>_h - sc_j, a node-wise dot product taken after this pass
+// (mp_gat_backward_epilogue_wide_f32).  Rows write acc to out, acc2 to out2 and
+// sc to ga; every lane of a head holds the same sc.  Elementwise per slot:
+// FMA and the hardware exp (gradients are tolerance-checked).
+template <int VEC, bool DR = false>
+struct GatBwdWideRed : RedFlags {
+  static constexpr bool kEid = DR;  // the dropout key: each edge's dst-CSR slot
+  static constexpr bool kGatWide = true;
+  static constexpr bool kDrop = DR;
+  static constexpr bool kStat = true;
+  struct Part {
+    float v[VEC];
+    float v2[VEC];
+    float s;
+  };
+  float acc[VEC], acc2[VEC];
+  float sc, as;
+  int h;
+
+  __device__ GatBwdWideRed(const AggArgs& p, int f, bool act) : h(act ? f / p.C : 0) {}
+
+  __device__ __forceinline__ void begin(const AggArgs& p, int64_t row, bool, int, bool) {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) acc[k] = acc2[k] = 0.f;
+    sc = 0.f;
+    as = p.a_src[row * p.H + h];
+  }
+  __device__ __forceinline__ void consume_gatw(const AggArgs& p, const Frag<VEC>& v, f32x4 q,
+                                               [[maybe_unused]] uint32_t dbits) {
+    const float score = as + q.x;
+    const float lk = score > 0.f ? 1.f : p.slope;
+    const float alpha = __expf(score * lk - q.y) * q.z;
+    // one-hot softmax row (see GatBwdRed::consume_gatb): its d score is 0, so the edge adds
+    // nothing to d a_src's two node-wise sums (acc2, sc)
+    const bool one_hot = q.z == 1.f && alpha == 1.f;
+    sc = one_hot ? sc : __builtin_fmaf(lk * alpha, q.w, sc);
+    float aw = alpha;
+    if constexpr (DR) aw = alpha * drop_factor(p, dbits, h);
+    const float law = one_hot ? 0.f : lk * aw;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      acc[k] = __builtin_fmaf(aw, v.v[k], acc[k]);
+      acc2[k] = __builtin_fmaf(law, v.v[k], acc2[k]);
+    }
+  }
+  __device__ __forceinline__ void consume(const Frag<VEC>&, float, int, float) {}
+  __device__ __forceinline__ void save(PRef r, bool stat_writer) const {
+    Frag<VEC> o;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) o.v[k] = acc[k];
+    store_frag<VEC>(r.v, o);
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) o.v[k] = acc2[k];
+    store_frag<VEC>(r.v2, o);
+    if (stat_writer) r.st[0] = sc;
+  }
+  static __device__ __forceinline__ Part load(PRef r) {
+    Frag<VEC> o = load_frag<VEC>(r.v);
+    Frag<VEC> o2 = load_frag<VEC>(r.v2);
+    Part q;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      q.v[k] = o.v[k];
+      q.v2[k] = o2.v[k];
+    }
+    q.s = r.st[0];
+    return q;
+  }
+  __device__ __forceinline__ void set(const Part& q) {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      acc[k] = q.v[k];
+      acc2[k] = q.v2[k];
+    }
+    sc = q.s;
+  }
+  __device__ __forceinline__ void merge(const Part& q) {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      acc[k] += q.v[k];
+      acc2[k] += q.v2[k];
+    }
+    sc += q.s;
+  }
+  __device__ __forceinline__ Part part() const {
+    Part q;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      q.v[k] = acc[k];
+      q.v2[k] = acc2[k];
+    }
+    q.s = sc;
+    return q;
+  }
+  __device__ __forceinline__ void finish(const AggArgs& p, int64_t row, int64_t, int f, bool act, bool with_bias = true) {
+    if (!act) return;
+    Frag<VEC> o;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) o.v[k] = acc[k];
+    store_out<VEC>(p.out + row * p.ldo + f, o);
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) o.v[k] = acc2[k];
+    store_out<VEC>(p.out2 + row * (int64_t)p.F + f, o);
+    if (f % p.C == 0) p.ga[row * p.H + h] = sc;
+  }
+};
+
 }  // namespace mp
 
 using namespace mp;
@@ -188,6 +303,52 @@ int mp_gat_backward_epilogue_wide_f32(float* grad_xw, const float* acc2, const f
       grad_xw, acc2, xw, att, grad_a_dst, sc_grad_a_src, n, H, C);
   MP_CHECK_LAUNCH();
   return MP_OK;
+}
+
+int mp_gat_backward_wide_f32(const mp_csr* gt, const float* grad_out, int64_t ldg, const float* a_src,
+                             const float* pack, int32_t H, int32_t C, float slope, uint64_t seed, float p_drop,
+                             const int32_t* drop_ids, float* grad_xw, float* acc2, size_t acc2_bytes, float* sc, size_t sc_bytes, void* slab,
+                             size_t slab_bytes, int32_t stages, void* stream) {
+  MP_DEVICE_GUARD(stream);
+  int rc = check_graph(gt, "mp_gat_backward_wide_f32");
+  if (rc) return rc;
+  MP_CHECK_ARG(H > 0 && C > 0 && C % 4 == 0, "mp_gat_backward_wide_f32: needs C %% 4 == 0");
+  if (p_drop > 0.f) {
+    rc = drop_check(p_drop, H, "mp_gat_backward_wide_f32");
+    if (rc) return rc;
+  }
+  MP_CHECK_ARG(grad_out && a_src && pack && grad_xw && acc2 && sc, "mp_gat_backward_wide_f32: null pointer");
+  const int F = H * C;
+  MP_CHECK_ARG(ldg >= F && ldg % 4 == 0, "mp_gat_backward_wide_f32: ldg < H*C or not a multiple of 4");
+  MP_CHECK_ARG((uintptr_t)grad_out % 16 == 0 && (uintptr_t)grad_xw % 16 == 0 && (uintptr_t)acc2 % 16 == 0 &&
+                   (uintptr_t)pack % 16 == 0,
+               "mp_gat_backward_wide_f32: grad_out, grad_xw, acc2, pack must be 16-byte aligned");
+  MP_CHECK_ARG(slab && slab_bytes >= mp_gat_train_slab_bytes(gt, H, C),
+               "mp_gat_backward_wide_f32: slab workspace too small (mp_gat_train_slab_bytes)");
+  MP_CHECK_EXTENT("mp_gat_backward_wide_f32", "acc2", acc2_bytes, (size_t)gt->n_rows * F * 4);
+  MP_CHECK_EXTENT("mp_gat_backward_wide_f32", "sc", sc_bytes, (size_t)gt->n_rows * H * 4);
+  AggArgs a{};
+  fill_graph(a, gt);
+  a.F = F;
+  a.x = grad_out;
+  a.ldx = ldg;
+  a.out = grad_xw;
+  a.ldo = F;
+  a.out2 = acc2;
+  a.ga = sc;
+  a.a_src = a_src;
+  a.pack = reinterpret_cast<const f32x4*>(pack);
+  a.H = H;
+  a.C = C;
+  a.slope = slope;
+  carve_slabs(a, slab, kSlabStat | kSlabV2);
+  hipStream_t s = as_stream(stream);
+  const int lanes = F >= 256 ? 64 : (F / 4 <= 4 ? 4 : next_pow2(F / 4));
+  if (p_drop > 0.f) {
+    set_drop(a, seed, p_drop, drop_ids);
+    return launch<GatBwdWideRed<4, true>, 4>(a, stages, s, lanes);
+  }
+  return launch<GatBwdWideRed<4>, 4>(a, stages, s, lanes);
 }
 
 }  // extern "C"

@@ -337,7 +337,7 @@ def test_any_dtype_loop_matches_c_loop_and_kats(reduce):
 
 def test_gat_dropout_keep_hash_restatement():
     """oracle.pyg_ref.gat_dropout_keep_slots (numpy, vectorised) against a
-    plain-int restatement of csrc/mp_aggregate.hip drop_hash, including a seed
+    plain-int restatement of csrc/mp_agg.h drop_hash, including a seed
     with high bits and slot*H + h past 2^32; keep fraction ~ 1 - p; the oracle
     layer with an all-keep mask scales the messages by 1/(1-p)."""
     M = 0xFFFFFFFF

@@ -264,8 +264,22 @@ def test_spline_abi_rejections_under_asan():
 
 
 def test_makefile_variant_rule_links_the_spline_object():
-    """A/B variant libraries are linked from an explicit object list: without
-    mp_spline.o they lack the new symbols and _lib.load() fails on them."""
+    """An A/B variant library must hold every unit of the main one (without
+    mp_spline.o or mp_gemm.o it lacks symbols and _lib.load() fails on it), each
+    compiled with the variant's DEFS: a knob may live in any unit."""
     mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert "mp_spline.hip" in re.search(r"^SRCS := (.*)$", mk, flags=re.M).group(1)
-    assert "build/mp_spline.o" in mk.split("variant: build/mp_version.o")[1]
+    units = [u[:-len(".hip")] for u in re.search(r"^SRCS := (.*)$", mk, flags=re.M).group(1).split()]
+    assert "mp_spline" in units and "mp_gemm" in units
+    assert sorted(u + ".hip" for u in units) == sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
+    r = subprocess.run(["make", "-n", "-C", CSRC, "variant", "NAME=t", "DEFS=-DMP_TEST_KNOB=3"],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    lines = r.stdout.splitlines()
+    link = [ln for ln in lines if "-shared" in ln and "lib_t.so" in ln]
+    assert len(link) == 1, r.stdout[-4000:]
+    objs = [w for w in link[0].split() if w.endswith(".o")]
+    assert sorted(objs) == sorted(["build/v_t/%s.o" % u for u in units] + ["build/mp_version.o"]), link[0]
+    for u in units:
+        cc = [ln for ln in lines if " -c %s.hip " % u in ln]
+        assert len(cc) == 1, (u, cc)
+        assert "-DMP_TEST_KNOB=3" in cc[0].split() and "build/v_t/%s.o" % u in cc[0].split(), cc[0]
