@@ -141,7 +141,10 @@ const char* mp_source_hash(void);
  *     256-feature tiles), 2 or 1 (128- / 64-feature XCD-affine tiles, taken
  *     when a head fits inside one tile).  The exception to the rule above:
  *     the per-slot <g_i, xw_j> sums its features in another order, so the
- *     gradients agree to rounding, not bit for bit. */
+ *     gradients agree to rounding, not bit for bit.
+ *   MP_TUNE_TOPK_WG_LIMIT: the largest graph (nodes) mp_topk_select_f32 ranks
+ *     by counting inside one workgroup (default 2048; 64..8192, else -1);
+ *     larger graphs are sorted.  mp_topk_path reports the path of a size. */
 #define MP_TUNE_FLAT_VEC1_MIN_BYTES 1
 #define MP_TUNE_FLAT_SMEM 2
 #define MP_TUNE_FLAT_MIN_F 3
@@ -152,6 +155,7 @@ const char* mp_source_hash(void);
 #define MP_TUNE_FLAT_SEQ_TILES 8
 #define MP_TUNE_FLAT_FAR_MIN_BYTES 9
 #define MP_TUNE_GAT_BWD_VEC 10
+#define MP_TUNE_TOPK_WG_LIMIT 11
 int64_t mp_tune(int32_t key, int64_t value);
 
 /* ---- CSR build (replaces the sort/bucketing torch_scatter never did: upstream
@@ -664,6 +668,108 @@ int mp_spline_aggregate_gather_f32(const mp_csr* g, const float* pseudo, int64_t
                                    const int32_t* kernel_size, const int32_t* is_open, int32_t degree,
                                    const float* x, int64_t ldx, int32_t F, const float* row_scale,
                                    const float* bias, float* out, int64_t ldo, void* stream);
+
+/* ---- TopKPooling: score, per-graph select, gate, filter_adj (csrc/mp_pool.hip)
+ * PyG 1.4.3 nn.pool.topk_pool [U] as one deterministic native path: no atomics
+ * on values (two integer counters and one integer maximum aside), no dense
+ * [G, max_nodes] copy, no host loop over the batch.  The caller allocates every
+ * output and workspace; every caller-sized array travels with its extent in
+ * bytes, checked before any launch.  n < 2^31 nodes and edges.
+ *
+ * Batch vector (non-decreasing int64 [n]):
+ *   mp_batch_stats: stats (device int64[3]) = { batch[n-1] + 1 (the number of
+ *     graphs), the longest run of equal ids (the largest graph), the number of
+ *     descents batch[i] < batch[i-1] plus 1 when batch[0] < 0 (0 = usable) }.
+ *   mp_batch_starts: starts[g] = first i with batch[i] >= g for g < n_graphs,
+ *     starts[n_graphs] = n (the convention of mp_segment_ids_i64; an id no node
+ *     carries is an empty graph).
+ *
+ * Score (attn [n, F] fp32, ld >= F; w [F]):
+ *   z = <attn[i, :], w>;  u = z / ||w||_2 (MP_POOL_SCORE_RAW: u = z);
+ *   score[i] = tanh(u) with MP_POOL_SCORE_TANH, else u.
+ *   ||w|| is summed on the device in a fixed order (no host read).  Rows of up
+ *   to 32 features share a wave (64 / pow2(F) rows each).
+ *   mp_pool_score_bwd_f32, du = g_score * f'(u) (1 - score^2 for tanh):
+ *     g_attn[i, :] = (du_i / ||w||) * w                     (NULL: skipped)
+ *     g_w = (sum_i du_i attn_i) / ||w|| - (sum_i du_i z_i) * w / ||w||^3
+ *   (RAW: g_attn = du * w, g_w = sum_i du_i attn_i), both sums through
+ *   mp_pool_score_bwd_parts(n) per-chunk partials added in chunk order.
+ *   ws: mp_pool_score_bwd_workspace(n, F) bytes.
+ *
+ * Select (score [n], starts [n_graphs + 1], ratio in (0, 1]):
+ *   graph g of n_g = starts[g+1] - starts[g] nodes keeps
+ *     k_g = min(n_g, ceil(fl32(ratio * fl32(n_g))))   (one fp32 multiply; upstream's
+ *     (ratio * num_nodes.to(torch.float)).ceil(), e.g. (0.3, 50) -> 16),
+ *   its nodes ranked by descending score, equal scores by ascending index
+ *   (-0 == +0; NaN above +inf, NaNs among themselves by index):
+ *     perm[out_starts[g] + r] = the node of rank r < k_g   (global ids),
+ *     out_starts = the exclusive scan of k_g, out_starts[n_graphs] = K,
+ *     inv[i] = the output position of node i, or -1 when it is dropped
+ *              (every entry written: no memset),
+ *     counts[0] = K (device int64; -1 when a graph is larger than max_n).
+ *   mp_topk_path(n_g): 0 = one wave ranks the graph by counting (n_g <= 64),
+ *   1 = one workgroup, keys in LDS (n_g <= MP_TUNE_TOPK_WG_LIMIT), 2 = sorted
+ *   (rocPRIM radix sort of (key, ~local index): device-wide when n_graphs == 1,
+ *   else one segment per over-limit graph).  max_n: an upper bound of the
+ *   largest n_g (n always is one); it sizes the LDS and decides whether the
+ *   sorted path is launched.  perm holds n entries (its upper bound).
+ *   mp_topk_counts: out_starts / counts[0] alone (no score is read).
+ *
+ * Gate (perm [k], k known to the host):
+ *   x_out[r, :] = x[perm[r], :] * score[perm[r]], then multiplier * that (a
+ *   second rounding) only when multiplier != 1; score_out[r] = score[perm[r]];
+ *   batch_out[r] = batch[perm[r]] (batch NULL: 0; batch_out NULL: skipped).
+ *   mp_pool_gate_bwd_f32: one pass over all n nodes, every row written once:
+ *     g_x[i, :] = (m * s_i) * g_y[inv[i], :],  g_s[i] = m * <g_y[inv[i]], x_i> + g_t[inv[i]]
+ *   and exact zeros for a dropped node (inv[i] < 0).  g_t NULL = zeros.
+ *
+ * filter_adj:
+ *   mp_pool_inverse: inv[perm[r]] = r for r < k, -1 elsewhere (for a perm that
+ *     did not come from mp_topk_select_f32).  k_dev (device int64, or NULL): the
+ *     count when only the device knows it yet; k is then its upper bound.
+ *   mp_pool_compact: out_pos = the positions i < n with keep[i] != 0, ascending;
+ *     count_dev[0] = their number.  (The min_score path's nonzero().)
+ *   mp_pool_filter_adj: edge e is kept iff inv[row[e]] >= 0 and inv[col[e]] >= 0;
+ *     kept edges in original order: out_row / out_col = inv[...] (int64),
+ *     out_pos[k] = the original position of output edge k (edge_attr and its
+ *     gradient); counts[1] = kept edges, counts[2] = edge ends outside
+ *     [0, n_nodes) (such edges are dropped; upstream raises IndexError, and so
+ *     must the caller).  The three outputs hold n_edges entries each
+ *     (out_bytes: the extent of each). */
+#define MP_POOL_SCORE_TANH 1
+#define MP_POOL_SCORE_RAW 2
+int mp_topk_path(int64_t n_g);
+int mp_batch_stats(const int64_t* batch, int64_t n, int64_t* stats, size_t stats_bytes, void* stream);
+int mp_batch_starts(const int64_t* batch, int64_t n, int64_t n_graphs, int64_t* starts, size_t starts_bytes,
+                    void* stream);
+int mp_pool_score_f32(const float* attn, int64_t ld, int64_t n, int32_t F, const float* w, int32_t flags,
+                      float* score, size_t score_bytes, void* stream);
+int32_t mp_pool_score_bwd_parts(int64_t n);
+size_t mp_pool_score_bwd_workspace(int64_t n, int32_t F);
+int mp_pool_score_bwd_f32(const float* attn, int64_t ld, int64_t n, int32_t F, const float* w, int32_t flags,
+                          const float* score, const float* g_score, float* g_attn, int64_t ldg, float* g_w,
+                          size_t g_w_bytes, void* ws, size_t ws_bytes, void* stream);
+int mp_topk_counts(const int64_t* starts, int64_t n_graphs, float ratio, int64_t max_n, int64_t* out_starts,
+                   size_t out_starts_bytes, int64_t* counts, void* stream);
+size_t mp_topk_workspace(int64_t n, int64_t n_graphs, int64_t max_n);
+int mp_topk_select_f32(const float* score, int64_t n, const int64_t* starts, int64_t n_graphs, int64_t max_n,
+                       float ratio, int64_t* perm, size_t perm_bytes, int64_t* out_starts, size_t out_starts_bytes,
+                       int64_t* inv, size_t inv_bytes, int64_t* counts, void* ws, size_t ws_bytes, void* stream);
+int mp_pool_gate_f32(const float* x, int64_t ldx, const float* score, const int64_t* batch, const int64_t* perm,
+                     int64_t k, int64_t n, int32_t F, float multiplier, float* x_out, int64_t ldo,
+                     size_t x_out_bytes, int64_t* batch_out, float* score_out, void* stream);
+int mp_pool_gate_bwd_f32(const float* g_y, int64_t ldgy, const float* g_t, const float* x, int64_t ldx,
+                         const float* score, const int64_t* inv, int64_t k, int64_t n, int32_t F, float multiplier,
+                         float* g_x, int64_t ldgx, size_t g_x_bytes, float* g_s, size_t g_s_bytes, void* stream);
+int mp_pool_inverse(const int64_t* perm, int64_t k, const int64_t* k_dev, int64_t n, int64_t* inv, size_t inv_bytes,
+                    void* stream);
+size_t mp_pool_compact_workspace(int64_t n);
+int mp_pool_compact(const uint8_t* keep, int64_t n, int64_t* out_pos, size_t out_pos_bytes, int64_t* count_dev,
+                    void* ws, size_t ws_bytes, void* stream);
+size_t mp_pool_filter_workspace(int64_t n_edges);
+int mp_pool_filter_adj(const int64_t* row, const int64_t* col, int64_t n_edges, const int64_t* inv, int64_t n_nodes,
+                       int64_t* out_row, int64_t* out_col, int64_t* out_pos, size_t out_bytes, int64_t* counts,
+                       void* ws, size_t ws_bytes, void* stream);
 
 /* ---- other dtypes (csrc/mp_dtype.hip) -------------------------------------
  * torch_scatter 2.0.4 reduces any dtype ([U8/U9]); the fp32 hot path is

@@ -923,6 +923,7 @@ struct Tune {
   std::atomic<int64_t> flat_seq_tiles{0};
   std::atomic<int64_t> flat_far_min_bytes{256ll << 20};  // the Infinity Cache
   std::atomic<int64_t> gat_bwd_vec{4};  // features per lane of the GAT backward's transposed pass
+  std::atomic<int64_t> topk_wg_limit{2048};  // largest graph mp_topk_select_f32 ranks in one workgroup (mp_pool.hip)
 };
 static Tune g_tune;
 
@@ -938,6 +939,7 @@ static std::atomic<int64_t>* tune_slot(int32_t key) {
     case MP_TUNE_FLAT_SEQ_TILES: return &g_tune.flat_seq_tiles;
     case MP_TUNE_FLAT_FAR_MIN_BYTES: return &g_tune.flat_far_min_bytes;
     case MP_TUNE_GAT_BWD_VEC: return &g_tune.gat_bwd_vec;
+    case MP_TUNE_TOPK_WG_LIMIT: return &g_tune.topk_wg_limit;
   }
   return nullptr;
 }
@@ -945,6 +947,7 @@ static std::atomic<int64_t>* tune_slot(int32_t key) {
 static inline int64_t tuned(std::atomic<int64_t>& v) { return v.load(std::memory_order_relaxed); }
 
 int64_t tuned_gat_bwd_vec() { return tuned(g_tune.gat_bwd_vec); }
+int64_t tuned_topk_wg_limit() { return tuned(g_tune.topk_wg_limit); }
 
 // Shape selection and launch of one mp_aggregate_f32 call (args checked).
 static int aggregate_dispatch(AggArgs& a, const mp_csr* g, int reduce, int stages, hipStream_t s) {
@@ -1031,6 +1034,7 @@ int64_t mp_tune(int32_t key, int64_t value) {
   if ((key == MP_TUNE_FLAT_VEC || key == MP_TUNE_FLAT_VEC_ARG || key == MP_TUNE_GAT_BWD_VEC) && value != 1 &&
       value != 2 && value != 4)
     return -1;
+  if (key == MP_TUNE_TOPK_WG_LIMIT && (value < 64 || value > 8192)) return -1;
   return v->exchange(value);
 }
 

@@ -11,6 +11,9 @@ namespace mp {
 
 void set_error(const char* fmt, ...);
 
+// MP_TUNE_TOPK_WG_LIMIT of the one mp_tune table (mp_aggregate.hip)
+int64_t tuned_topk_wg_limit();
+
 #define MP_CHECK_ARG(cond, ...)        \
   do {                                 \
     if (!(cond)) {                     \

@@ -33,6 +33,9 @@ MP_TUNE_FLAT_VEC_ARG = 7
 MP_TUNE_FLAT_SEQ_TILES = 8
 MP_TUNE_FLAT_FAR_MIN_BYTES = 9
 MP_TUNE_GAT_BWD_VEC = 10
+MP_TUNE_TOPK_WG_LIMIT = 11
+MP_POOL_SCORE_TANH = 1
+MP_POOL_SCORE_RAW = 2
 MP_DTYPE = {torch.float32: 0, torch.float64: 1, torch.float16: 2, torch.bfloat16: 3, torch.int64: 4}
 MP_LOOPS_REMOVE = 0
 MP_LOOPS_ADD = 1
@@ -155,6 +158,26 @@ SIGNATURES = {
                                                     i32, c_p, c_p, i64, c_p]),
     "mp_spline_aggregate_gather_f32": (ctypes.c_int, [ctypes.POINTER(MpCsr), c_p, i64, i32, c_p, c_p, i32, c_p, i64,
                                                       i32, c_p, c_p, c_p, i64, c_p]),
+    "mp_topk_path": (ctypes.c_int, [i64]),
+    "mp_batch_stats": (ctypes.c_int, [c_p, i64, c_p, sz, c_p]),
+    "mp_batch_starts": (ctypes.c_int, [c_p, i64, i64, c_p, sz, c_p]),
+    "mp_pool_score_f32": (ctypes.c_int, [c_p, i64, i64, i32, c_p, i32, c_p, sz, c_p]),
+    "mp_pool_score_bwd_parts": (i32, [i64]),
+    "mp_pool_score_bwd_workspace": (sz, [i64, i32]),
+    "mp_pool_score_bwd_f32": (ctypes.c_int, [c_p, i64, i64, i32, c_p, i32, c_p, c_p, c_p, i64, c_p, sz, c_p, sz,
+                                             c_p]),
+    "mp_topk_counts": (ctypes.c_int, [c_p, i64, f32, i64, c_p, sz, c_p, c_p]),
+    "mp_topk_workspace": (sz, [i64, i64, i64]),
+    "mp_topk_select_f32": (ctypes.c_int, [c_p, i64, c_p, i64, i64, f32, c_p, sz, c_p, sz, c_p, sz, c_p, c_p, sz,
+                                          c_p]),
+    "mp_pool_gate_f32": (ctypes.c_int, [c_p, i64, c_p, c_p, c_p, i64, i64, i32, f32, c_p, i64, sz, c_p, c_p, c_p]),
+    "mp_pool_gate_bwd_f32": (ctypes.c_int, [c_p, i64, c_p, c_p, i64, c_p, c_p, i64, i64, i32, f32, c_p, i64, sz,
+                                            c_p, sz, c_p]),
+    "mp_pool_inverse": (ctypes.c_int, [c_p, i64, c_p, i64, c_p, sz, c_p]),
+    "mp_pool_compact_workspace": (sz, [i64]),
+    "mp_pool_compact": (ctypes.c_int, [c_p, i64, c_p, sz, c_p, c_p, sz, c_p]),
+    "mp_pool_filter_workspace": (sz, [i64]),
+    "mp_pool_filter_adj": (ctypes.c_int, [c_p, c_p, i64, c_p, i64, c_p, c_p, c_p, sz, c_p, c_p, sz, c_p]),
 }
 
 _lib = None

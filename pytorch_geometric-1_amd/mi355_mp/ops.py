@@ -1508,3 +1508,336 @@ def spline_propagate(graph, x, weight, pseudo, kernel_size, is_open_spline, degr
         form = spline_form(geom[3], weight.shape[1], weight.shape[2], geom[2])
     reduce = "add" if reduce == "sum" else reduce
     return _SplinePropagate.apply(x, weight, bias, graph, pseudo, geom, int(degree), reduce, form)
+
+
+# ---------------------------------------------------------------------------
+# TopKPooling (PyG 1.4.3 nn.pool.topk_pool [U]; csrc/mp_pool.hip)
+# ---------------------------------------------------------------------------
+
+class BatchLayout(object):
+    """A non-decreasing batch vector as segment starts: starts [G + 1] (device
+    int64, starts[G] = n), G graphs, max_n = the largest graph, unsorted = the
+    number of descents (0 for a usable batch)."""
+    __slots__ = ("starts", "n_graphs", "max_n", "unsorted", "n")
+
+    def __init__(self, starts, n_graphs, max_n, unsorted, n):
+        self.starts, self.n_graphs, self.max_n, self.unsorted, self.n = starts, n_graphs, max_n, unsorted, n
+
+
+def check_ratio(ratio):
+    """ratio in (0, 1]: upstream indexes into the padding of its dense copy otherwise."""
+    if not (0.0 < float(ratio) <= 1.0):
+        raise ValueError("TopKPooling: ratio must lie in (0, 1] (got %r)" % (ratio,))
+    return float(ratio)
+
+
+def topk_path(n_g):
+    """0 = one wave, 1 = one workgroup, 2 = sorted: how mp_topk_select_f32 ranks a
+    graph of n_g nodes (mp_topk_path; needs no GPU)."""
+    return int(_lib.load().mp_topk_path(int(n_g)))
+
+
+def batch_layout(batch, n, device=None):
+    """BatchLayout of `batch` ([n] int64 on the device, or None = one graph).
+    One host read (graphs, largest graph and sortedness together); none for
+    batch None."""
+    lib = _lib.load()
+    n = int(n)
+    if batch is None:
+        starts = torch.tensor([0, n], dtype=torch.int64).to(device)
+        return BatchLayout(starts, 1, n, 0, n)
+    _lib.require_device(batch)
+    if batch.dtype != torch.int64 or batch.dim() != 1 or batch.shape[0] != n:
+        raise ValueError("mi355_mp: batch must be int64 [%d] (got %s %s)" % (n, batch.dtype, tuple(batch.shape)))
+    batch = batch.contiguous()
+    dev = batch.device
+    st = _lib.stream_ptr(dev)
+    stats = torch.empty(3, dtype=torch.int64, device=dev)
+    _lib.check(lib.mp_batch_stats(batch.data_ptr(), n, stats.data_ptr(), _lib.nbytes(stats), st), "mp_batch_stats")
+    G, max_n, unsorted = stats.tolist()
+    starts = torch.empty(G + 1, dtype=torch.int64, device=dev)
+    _lib.check(lib.mp_batch_starts(batch.data_ptr(), n, G, starts.data_ptr(), _lib.nbytes(starts), st),
+               "mp_batch_starts")
+    return BatchLayout(starts, G, min(max_n, n), unsorted, n)
+
+
+def _pool_rows(x, what):
+    x = _f32_2d(x, what)
+    if x.shape[1] < 1:
+        raise ValueError("mi355_mp: %s needs at least one feature" % what)
+    if x.stride(0) < x.shape[1]:
+        x = x.contiguous()
+    return x
+
+
+class _PoolScore(torch.autograd.Function):
+    """score = f(<attn, w> / ||w||) (mp_pool_score_f32) and its backward
+    (mp_pool_score_bwd_f32: g_attn rows, g_w through fixed-order partials)."""
+
+    @staticmethod
+    def forward(ctx, attn, weight, flags):
+        lib = _lib.load()
+        attn = _pool_rows(attn, "attn")
+        w = weight.detach().reshape(-1).contiguous()
+        n, F = attn.shape
+        if w.dtype != torch.float32 or w.numel() != F:
+            raise ValueError("mi355_mp: weight must be float32 with %d entries (got %s %s)"
+                             % (F, weight.dtype, tuple(weight.shape)))
+        score = torch.empty(n, dtype=torch.float32, device=attn.device)
+        _lib.check(lib.mp_pool_score_f32(attn.data_ptr(), attn.stride(0), n, F, w.data_ptr(), flags, score.data_ptr(),
+                                         _lib.nbytes(score), _lib.stream_ptr(attn.device)), "mp_pool_score_f32")
+        ctx.flags = flags
+        ctx.wshape = weight.shape
+        ctx.save_for_backward(attn, w, score)
+        return score
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        attn, w, score = ctx.saved_tensors
+        n, F = attn.shape
+        dev = attn.device
+        g = g.contiguous()
+        g_attn = torch.empty((n, F), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        g_w = torch.empty(F, dtype=torch.float32, device=dev)
+        wsb = lib.mp_pool_score_bwd_workspace(n, F)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        _lib.check(lib.mp_pool_score_bwd_f32(attn.data_ptr(), attn.stride(0), n, F, w.data_ptr(), ctx.flags,
+                                             score.data_ptr(), g.data_ptr(), _lib.ptr(g_attn), F, g_w.data_ptr(),
+                                             _lib.nbytes(g_w), ws.data_ptr(), wsb, _lib.stream_ptr(dev)),
+                   "mp_pool_score_bwd_f32")
+        return g_attn, (g_w.view(ctx.wshape) if ctx.needs_input_grad[1] else None), None
+
+
+def pool_score(attn, weight, tanh=True, raw=False):
+    """score [n] = f(<attn[i], w> / ||w||_2), f = tanh or the identity; raw: the
+    bare projection <attn[i], w> (the min_score path).  Differentiable in attn
+    and weight; ||w|| is computed on the device."""
+    _lib.require_device(attn, weight)
+    flags = (_lib.MP_POOL_SCORE_TANH if tanh else 0) | (_lib.MP_POOL_SCORE_RAW if raw else 0)
+    return _PoolScore.apply(attn, weight, flags)
+
+
+def topk_counts(starts, ratio, max_n=None):
+    """(out_starts [G + 1], counts [4]) of mp_topk_counts: the exclusive scan of
+    the device's k_g = ceil(fl32(ratio * fl32(n_g))) and K; no host read."""
+    _lib.require_device(starts)
+    G = starts.numel() - 1
+    out_starts = torch.empty(G + 1, dtype=torch.int64, device=starts.device)
+    counts = torch.zeros(4, dtype=torch.int64, device=starts.device)
+    _lib.check(_lib.load().mp_topk_counts(starts.data_ptr(), G, check_ratio(ratio),
+                                          (1 << 62) if max_n is None else int(max_n), out_starts.data_ptr(),
+                                          _lib.nbytes(out_starts), counts.data_ptr(),
+                                          _lib.stream_ptr(starts.device)), "mp_topk_counts")
+    return out_starts, counts
+
+
+class PoolSelection(object):
+    """What a select leaves on the device: perm (sized n, its first K entries
+    valid), out_starts [G + 1] (None on the min_score path), inv [n] and counts
+    (int64[4]: K, then filter_adj's kept edges and bad edge ends)."""
+    __slots__ = ("perm", "out_starts", "inv", "counts")
+
+    def __init__(self, perm, out_starts, inv, counts):
+        self.perm, self.out_starts, self.inv, self.counts = perm, out_starts, inv, counts
+
+
+def topk_select(score, ratio, layout):
+    """Per-graph top-k of score [n] (mp_topk_select_f32): ceil(ratio * n_g) nodes
+    of every graph by descending score, equal scores by ascending index.  No
+    host read: K stays in counts[0]."""
+    _lib.require_device(score)
+    lib = _lib.load()
+    ratio = check_ratio(ratio)
+    score = score.detach()
+    if score.dtype != torch.float32 or score.dim() != 1 or score.shape[0] != layout.n:
+        raise ValueError("mi355_mp: score must be float32 [%d] (got %s %s)" % (layout.n, score.dtype, tuple(score.shape)))
+    score = score.contiguous()
+    dev = score.device
+    n, G = layout.n, layout.n_graphs
+    perm = torch.empty(n, dtype=torch.int64, device=dev)
+    inv = torch.empty(n, dtype=torch.int64, device=dev)
+    out_starts = torch.empty(G + 1, dtype=torch.int64, device=dev)
+    counts = torch.zeros(4, dtype=torch.int64, device=dev)
+    wsb = lib.mp_topk_workspace(n, G, layout.max_n)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    _lib.check(lib.mp_topk_select_f32(score.data_ptr(), n, layout.starts.data_ptr(), G, layout.max_n, ratio,
+                                      perm.data_ptr(), _lib.nbytes(perm), out_starts.data_ptr(),
+                                      _lib.nbytes(out_starts), inv.data_ptr(), _lib.nbytes(inv), counts.data_ptr(),
+                                      ws.data_ptr(), wsb, _lib.stream_ptr(dev)), "mp_topk_select_f32")
+    return PoolSelection(perm, out_starts, inv, counts)
+
+
+def pool_compact(keep, counts=None):
+    """(pos, counts): pos[:counts[0]] = the positions with keep != 0 in ascending
+    order (mp_pool_compact; pos is sized n).  No host read."""
+    _lib.require_device(keep)
+    lib = _lib.load()
+    keep = keep.to(torch.uint8).contiguous()
+    n = keep.numel()
+    dev = keep.device
+    pos = torch.empty(n, dtype=torch.int64, device=dev)
+    if counts is None:
+        counts = torch.zeros(4, dtype=torch.int64, device=dev)
+    wsb = lib.mp_pool_compact_workspace(n)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    _lib.check(lib.mp_pool_compact(keep.data_ptr(), n, pos.data_ptr(), _lib.nbytes(pos), counts.data_ptr(),
+                                   ws.data_ptr(), wsb, _lib.stream_ptr(dev)), "mp_pool_compact")
+    return pos, counts
+
+
+def pool_inverse(perm, n, k_dev=None):
+    """inv [n]: inv[perm[r]] = r, -1 elsewhere (mp_pool_inverse); k_dev: a device
+    count bounding r when the host does not know it yet."""
+    _lib.require_device(perm)
+    perm = perm.to(torch.int64).contiguous()
+    inv = torch.empty(int(n), dtype=torch.int64, device=perm.device)
+    _lib.check(_lib.load().mp_pool_inverse(perm.data_ptr(), min(perm.numel(), int(n)), _lib.ptr(k_dev), int(n),
+                                           inv.data_ptr(), _lib.nbytes(inv), _lib.stream_ptr(perm.device)),
+               "mp_pool_inverse")
+    return inv
+
+
+def select_min_score(score, min_score, batch, layout, tol=1e-7):
+    """upstream's min_score branch of topk: the nodes with
+    score > min(max_g(score) - tol, min_score), in ascending node order.  The
+    segment maximum and its gather are the engine's existing ops; the ordered
+    compaction and the inverse map are mp_pool_compact / mp_pool_inverse."""
+    _lib.require_device(score)
+    score = score.detach()
+    n = layout.n
+    if batch is None:
+        batch = torch.zeros(n, dtype=torch.int64, device=score.device)
+    mx, _ = segment_reduce(score.view(-1, 1), batch, layout.n_graphs, "max")
+    thr = (index_select_rows(mx, batch).view(-1) - tol).clamp(max=min_score)
+    pos, counts = pool_compact(score > thr)
+    inv = pool_inverse(pos, n, counts)
+    return PoolSelection(pos, None, inv, counts)
+
+
+def pool_filter_adj(edge_index, sel, n):
+    """Launch filter_adj against sel.inv (mp_pool_filter_adj): returns (out [2, E],
+    pos [E]) sized at their upper bound; sel.counts[1] = kept edges, [2] = edge
+    ends outside [0, n).  No host read."""
+    _lib.require_device(edge_index)
+    lib = _lib.load()
+    dev = edge_index.device
+    E = int(edge_index.shape[1])
+    row = edge_index[0].to(torch.int64).contiguous()
+    col = edge_index[1].to(torch.int64).contiguous()
+    out = torch.empty((2, E), dtype=torch.int64, device=dev)
+    pos = torch.empty(E, dtype=torch.int64, device=dev)
+    wsb = lib.mp_pool_filter_workspace(E)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    _lib.check(lib.mp_pool_filter_adj(row.data_ptr(), col.data_ptr(), E, sel.inv.data_ptr(), int(n),
+                                      out[0].data_ptr(), out[1].data_ptr(), pos.data_ptr(), E * 8,
+                                      sel.counts.data_ptr(), ws.data_ptr(), wsb, _lib.stream_ptr(dev)),
+               "mp_pool_filter_adj")
+    return out, pos
+
+
+def pool_read_counts(sel, n):
+    """The one host read after select and filter_adj: (K, kept edges).  Raises
+    IndexError when an edge end lay outside [0, n), as upstream's mask[row] does."""
+    K, kept, bad, _ = sel.counts.tolist()
+    if K < 0:
+        raise RuntimeError("mi355_mp: a graph is larger than the batch layout's max_n")
+    if bad:
+        raise IndexError("filter_adj: %d edge ends lie outside [0, %d)" % (bad, n))
+    return K, kept
+
+
+class _PoolGate(torch.autograd.Function):
+    """x_out = multiplier * (x[perm] * score[perm]), score_out = score[perm],
+    batch_out = batch[perm] (mp_pool_gate_f32); backward: one pass over all n
+    nodes through inv (mp_pool_gate_bwd_f32), zeros for dropped nodes."""
+
+    @staticmethod
+    def forward(ctx, x, score, perm, inv, batch, multiplier):
+        lib = _lib.load()
+        x = _pool_rows(x, "x")
+        score = score.contiguous()
+        n, F = x.shape
+        k = perm.numel()
+        dev = x.device
+        x_out = torch.empty((k, F), dtype=torch.float32, device=dev)
+        score_out = torch.empty(k, dtype=torch.float32, device=dev)
+        batch_out = torch.empty(k, dtype=torch.int64, device=dev)
+        _lib.check(lib.mp_pool_gate_f32(x.data_ptr(), x.stride(0), score.data_ptr(), _lib.ptr(batch), perm.data_ptr(),
+                                        k, n, F, float(multiplier), x_out.data_ptr(), F, _lib.nbytes(x_out),
+                                        batch_out.data_ptr(), score_out.data_ptr(), _lib.stream_ptr(dev)),
+                   "mp_pool_gate_f32")
+        ctx.k, ctx.multiplier = k, float(multiplier)
+        ctx.save_for_backward(x, score, inv)
+        ctx.mark_non_differentiable(batch_out)
+        return x_out, score_out, batch_out
+
+    @staticmethod
+    def backward(ctx, g_y, g_t, _g_b=None):
+        lib = _lib.load()
+        x, score, inv = ctx.saved_tensors
+        n, F = x.shape
+        dev = x.device
+        g_y = g_y.contiguous()
+        g_t = g_t.contiguous()
+        g_x = torch.empty((n, F), dtype=torch.float32, device=dev)
+        g_s = torch.empty(n, dtype=torch.float32, device=dev)
+        _lib.check(lib.mp_pool_gate_bwd_f32(g_y.data_ptr(), F, g_t.data_ptr(), x.data_ptr(), x.stride(0),
+                                            score.data_ptr(), inv.data_ptr(), ctx.k, n, F, ctx.multiplier,
+                                            g_x.data_ptr(), F, _lib.nbytes(g_x), g_s.data_ptr(), _lib.nbytes(g_s),
+                                            _lib.stream_ptr(dev)), "mp_pool_gate_bwd_f32")
+        return g_x, g_s, None, None, None, None
+
+
+def pool_gate(x, score, perm, inv, batch=None, multiplier=1):
+    """(x_out, score_out, batch_out) of the kept nodes perm (exact length K);
+    differentiable in x and score.  inv: the inverse map of perm over x's rows."""
+    _lib.require_device(x, score, perm, inv, batch)
+    if score.dtype != torch.float32 or score.dim() != 1 or score.shape[0] != x.shape[0]:
+        raise ValueError("mi355_mp: score must be float32 [%d]" % x.shape[0])
+    if batch is not None:
+        batch = batch.contiguous()
+    return _PoolGate.apply(x, score, perm.contiguous(), inv, batch, multiplier)
+
+
+class _GatherByPos(torch.autograd.Function):
+    """attr[pos] for distinct positions pos; the gradient scatters back by pos."""
+
+    @staticmethod
+    def forward(ctx, attr, pos):
+        ctx.n = attr.shape[0]
+        ctx.save_for_backward(pos)
+        return _gather_rows_bytes(attr, pos)
+
+    @staticmethod
+    def backward(ctx, g):
+        (pos,) = ctx.saved_tensors
+        out = torch.zeros((ctx.n,) + tuple(g.shape[1:]), dtype=g.dtype, device=g.device)
+        out.index_copy_(0, pos, g)
+        return out, None
+
+
+def _gather_rows_bytes(attr, pos):
+    """rows of any dtype whose elements are 2, 4 or 8 bytes wide (mp_gather_rows_any)."""
+    flat = attr.reshape(attr.shape[0], -1)
+    if flat.stride(1) != 1 or flat.stride(0) < max(flat.shape[1], 1):
+        flat = flat.contiguous()
+    if flat.element_size() not in (2, 4, 8):
+        raise TypeError("mi355_mp: edge_attr of dtype %s (%d-byte elements) is not supported"
+                        % (attr.dtype, flat.element_size()))
+    k, F = pos.numel(), flat.shape[1]
+    out = torch.empty((k, F), dtype=attr.dtype, device=attr.device)
+    if k and F:
+        _lib.check(_lib.load().mp_gather_rows_any(flat.element_size(), flat.data_ptr(), flat.stride(0), pos.data_ptr(),
+                                                  k, F, out.data_ptr(), F, _lib.stream_ptr(attr.device)),
+                   "mp_gather_rows_any")
+    return out.view((k,) + tuple(attr.shape[1:]))
+
+
+def pool_edge_attr(edge_attr, pos):
+    """edge_attr[pos] for filter_adj's kept positions (any trailing shape)."""
+    _lib.require_device(edge_attr, pos)
+    pos = pos.contiguous()
+    if edge_attr.requires_grad:
+        return _GatherByPos.apply(edge_attr, pos)
+    return _gather_rows_bytes(edge_attr, pos)

@@ -4,7 +4,7 @@ Pinned at /root/reference/requirement.txt:7 (torch-geometric==1.4.3); the
 reference tree only calls it (examples/gcn.py:5-7, ConvexPruning.py:12-19).
 Only the aggregation path is provided here: ``nn.MessagePassing``,
 ``nn.GCNConv``, ``nn.GATConv``, ``nn.SAGEConv``, ``nn.GraphConv``, global
-pooling, ``nn.DataParallel`` with the ``data`` containers it batches, and the
+pooling, ``nn.TopKPooling``, ``nn.DataParallel`` with the ``data`` containers it batches, and the
 ``utils`` they use.  Every aggregation runs on the MI355X engine
 (``mi355_mp``); there is no CPU fallback.
 """

@@ -1,7 +1,9 @@
 from .conv import MessagePassing, GCNConv, GATConv, SAGEConv, GraphConv, ChebConv, AGNNConv, SGConv, GINConv, SplineConv
 from .glob import global_add_pool, global_mean_pool, global_max_pool
+from .pool import TopKPooling
 from .data_parallel import DataParallel
 from . import inits  # noqa: F401
 
 __all__ = ["MessagePassing", "GCNConv", "GATConv", "SAGEConv", "GraphConv", "ChebConv", "AGNNConv", "SGConv",
-           "GINConv", "SplineConv", "global_add_pool", "global_mean_pool", "global_max_pool", "DataParallel"]
+           "GINConv", "SplineConv", "global_add_pool", "global_mean_pool", "global_max_pool", "TopKPooling",
+           "DataParallel"]
