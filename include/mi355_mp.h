@@ -771,6 +771,87 @@ int mp_pool_filter_adj(const int64_t* row, const int64_t* col, int64_t n_edges, 
                        int64_t* out_row, int64_t* out_col, int64_t* out_pos, size_t out_bytes, int64_t* counts,
                        void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Cluster pooling (csrc/mp_cluster.hip) ----------------------------------
+ * PyG 1.4.3 nn.pool voxel_grid / consecutive_cluster / max_pool / avg_pool /
+ * pool_edge [U] (torch_cluster 1.5 grid, torch_sparse 0.6.1 coalesce).  The
+ * caller allocates every output at its upper bound (n nodes, n_edges edges);
+ * the counts stay on the device (int64 counts[4]: [0] = M clusters, [1] = E'
+ * output edges, [2] = edge ends outside [0, n_nodes)) and every kernel that
+ * depends on one reads it there.  n, n_edges < 2^31.  No float atomics; every
+ * valid output entry is written (no memset by the caller).  The entry points are
+ * additions: the ABI version is unchanged.
+ *
+ * mp_voxel_keys_f32: key[i] = sum_d c_d * prod_{j<d} m_j (wrapping int64) over the
+ *   D columns of pos (leading dimension ldp) and, when batch is given, one more
+ *   column fl32(batch[i]); size / start / end: device fp32 [D (+ 1)];
+ *     c_d = (int64) trunc(fl32(fl32(p_d - start_d) / size_d)),
+ *     m_d = (int64) trunc(fl32(fl32(end_d - start_d) / size_d)) + 1
+ *   with IEEE fp32 subtraction and division.  D <= 8.  Positions outside
+ *   [start, end] follow the same arithmetic (keys may collide or be negative).
+ *
+ * mp_cluster_build: the consecutive relabelling of any int64 key [n]: one stable
+ *   radix sort of (key, node index) over the full signed key, the run heads and
+ *   their scan.  inv[i] = the rank of key[i] among the distinct keys (ascending,
+ *   signed); rowptr [n + 1] / member [n] (int32): cluster c owns member[rowptr[c]
+ *   .. rowptr[c + 1]), node indices ascending (rowptr's first M + 1 entries are
+ *   written); perm[c] = the largest node index of cluster c (first M entries);
+ *   counts[0] = M.
+ *
+ * mp_cluster_reduce_f32: one pass over the clusters of rowptr / member, M read
+ *   from counts[0]:
+ *     x_out[c, :] (leading dimension ldo) = MP_REDUCE_MAX: the maximum over the
+ *       members in ascending node order from lowest(), strict compare (the lowest
+ *       node index wins a tie); arg[c, f] (int64 [n, F] contiguous, or NULL) =
+ *       that node, or n when no member exceeded lowest() (the output is then 0);
+ *       MP_FLAG_PYG_MASK: out < -10000 := 0.  MP_REDUCE_MEAN: ((0 + x_0) + x_1)
+ *       + ... in ascending node order, divided by the member count.  F = 0: skipped.
+ *     pos_out[c, :] ([n, Dp] contiguous) = the mean of pos likewise (Dp = 0: skipped).
+ *     batch_out[c] = batch[perm[c]] (batch_out NULL: skipped).
+ *   A group of pow2(max(F, Dp)) <= 64 lanes owns a cluster (64 / that many
+ *   clusters per wave); the clusters are strided over at most
+ *   mp_cluster_max_blocks() workgroups.
+ *
+ * mp_cluster_edges: pool_edge's index side.  key = inv[row] * M + inv[col]; an
+ *   edge with inv[row] == inv[col] is dropped, an edge with an end outside
+ *   [0, n_nodes) is dropped and counted in counts[2] (the caller raises).  One
+ *   stable radix sort of (key, edge position) over 2 * ceil(log2 n_nodes) + 1
+ *   bits, the run heads and their scan:
+ *     out_row / out_col (int64 [n_edges], first E' valid) = the distinct pairs in
+ *       ascending row * M + col order; edge_slot[e] = the output position of
+ *       original edge e, or -1 when it was dropped (every entry written);
+ *     seg_ptr [n_edges + 1] / seg_edge [n_edges] (int32): output edge k collects
+ *       the original edges seg_edge[seg_ptr[k] .. seg_ptr[k + 1]), ascending;
+ *     counts[1] = E'.  counts[0] = M must already be on the device.
+ *   out_bytes: the extent of each of out_row, out_col and edge_slot.
+ *
+ * mp_cluster_edge_attr_f32: out[k, :] = ((0 + attr[e_0, :]) + attr[e_1, :]) + ...
+ *   over seg_edge of output edge k in order, for k < counts[1]; out holds
+ *   n_edges rows.  mp_cluster_edge_attr_bwd_f32: g_attr[e, :] = g[edge_slot[e], :]
+ *   for 0 <= edge_slot[e] < n_out, zeros otherwise (every row written). */
+int32_t mp_cluster_max_blocks(void);
+int mp_voxel_keys_f32(const float* pos, int64_t ldp, int64_t n, int32_t D, const int64_t* batch, const float* size,
+                      const float* start, const float* end, int64_t* key, size_t key_bytes, void* stream);
+size_t mp_cluster_build_workspace(int64_t n);
+int mp_cluster_build(const int64_t* key, int64_t n, int64_t* inv, size_t inv_bytes, int32_t* rowptr,
+                     size_t rowptr_bytes, int32_t* member, size_t member_bytes, int64_t* perm, size_t perm_bytes,
+                     int64_t* counts, void* ws, size_t ws_bytes, void* stream);
+int mp_cluster_reduce_f32(const float* x, int64_t ldx, int32_t F, int32_t reduce, int32_t flags,
+                          const int32_t* rowptr, const int32_t* member, const int64_t* counts, int64_t n,
+                          float* x_out, int64_t ldo, size_t x_out_bytes, int64_t* arg, size_t arg_bytes,
+                          const float* pos, int64_t ldp, int32_t Dp, float* pos_out, size_t pos_out_bytes,
+                          const int64_t* batch, const int64_t* perm, int64_t* batch_out, size_t batch_out_bytes,
+                          void* stream);
+size_t mp_cluster_edges_workspace(int64_t n_edges, int64_t n_nodes);
+int mp_cluster_edges(const int64_t* row, const int64_t* col, int64_t n_edges, const int64_t* inv, int64_t n_nodes,
+                     int64_t* counts, int64_t* out_row, int64_t* out_col, int64_t* edge_slot, size_t out_bytes,
+                     int32_t* seg_ptr, size_t seg_ptr_bytes, int32_t* seg_edge, size_t seg_edge_bytes, void* ws,
+                     size_t ws_bytes, void* stream);
+int mp_cluster_edge_attr_f32(const float* attr, int64_t lda, int32_t A, const int32_t* seg_ptr,
+                             const int32_t* seg_edge, const int64_t* counts, int64_t n_edges, float* out, int64_t ldo,
+                             size_t out_bytes, void* stream);
+int mp_cluster_edge_attr_bwd_f32(const float* g, int64_t ldg, const int64_t* edge_slot, int64_t n_edges, int32_t A,
+                                 int64_t n_out, float* g_attr, int64_t ldga, size_t g_attr_bytes, void* stream);
+
 /* ---- other dtypes (csrc/mp_dtype.hip) -------------------------------------
  * torch_scatter 2.0.4 reduces any dtype ([U8/U9]); the fp32 hot path is
  * mp_aggregate_f32, these are the breadth path for the rest. */

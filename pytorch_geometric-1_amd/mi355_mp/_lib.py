@@ -178,6 +178,17 @@ SIGNATURES = {
     "mp_pool_compact": (ctypes.c_int, [c_p, i64, c_p, sz, c_p, c_p, sz, c_p]),
     "mp_pool_filter_workspace": (sz, [i64]),
     "mp_pool_filter_adj": (ctypes.c_int, [c_p, c_p, i64, c_p, i64, c_p, c_p, c_p, sz, c_p, c_p, sz, c_p]),
+    "mp_cluster_max_blocks": (i32, []),
+    "mp_voxel_keys_f32": (ctypes.c_int, [c_p, i64, i64, i32, c_p, c_p, c_p, c_p, c_p, sz, c_p]),
+    "mp_cluster_build_workspace": (sz, [i64]),
+    "mp_cluster_build": (ctypes.c_int, [c_p, i64, c_p, sz, c_p, sz, c_p, sz, c_p, sz, c_p, c_p, sz, c_p]),
+    "mp_cluster_reduce_f32": (ctypes.c_int, [c_p, i64, i32, i32, i32, c_p, c_p, c_p, i64, c_p, i64, sz, c_p, sz,
+                                             c_p, i64, i32, c_p, sz, c_p, c_p, c_p, sz, c_p]),
+    "mp_cluster_edges_workspace": (sz, [i64, i64]),
+    "mp_cluster_edges": (ctypes.c_int, [c_p, c_p, i64, c_p, i64, c_p, c_p, c_p, c_p, sz, c_p, sz, c_p, sz, c_p, sz,
+                                        c_p]),
+    "mp_cluster_edge_attr_f32": (ctypes.c_int, [c_p, i64, i32, c_p, c_p, c_p, i64, c_p, i64, sz, c_p]),
+    "mp_cluster_edge_attr_bwd_f32": (ctypes.c_int, [c_p, i64, c_p, i64, i32, i64, c_p, i64, sz, c_p]),
 }
 
 _lib = None

@@ -1841,3 +1841,311 @@ def pool_edge_attr(edge_attr, pos):
     if edge_attr.requires_grad:
         return _GatherByPos.apply(edge_attr, pos)
     return _gather_rows_bytes(edge_attr, pos)
+
+
+# ---------------------------------------------------------------------------
+# Cluster pooling (PyG 1.4.3 nn.pool voxel_grid / max_pool / avg_pool [U]; csrc/mp_cluster.hip)
+# ---------------------------------------------------------------------------
+
+_layout_cache = _Cache()
+
+
+def cached_batch_layout(batch, n, device=None):
+    """batch_layout, cached on the batch tensor (identity + version counter, as
+    index_range): one host read the first time a batch vector is seen."""
+    if batch is None:
+        return batch_layout(None, n, device)
+    return _layout_cache.get(batch, ("layout", batch.data_ptr(), int(n)), lambda: batch_layout(batch, n, device))
+
+
+_graphs_cache = _Cache()
+
+
+def known_num_graphs(batch):
+    """batch.max() + 1 when the host already knows it for this batch tensor (a
+    cached layout, or note_num_graphs), else None.  Never reads."""
+    if batch is None:
+        return 1
+    return _graphs_cache.get(batch, ("graphs", batch.data_ptr()), lambda: None)
+
+
+def note_num_graphs(batch, n_graphs):
+    """Record batch.max() + 1 of a batch vector the engine derived from one whose
+    count it knew (a pooled batch keeps every graph that has a node)."""
+    if batch is not None and n_graphs is not None:
+        _graphs_cache.get(batch, ("graphs", batch.data_ptr()), lambda: int(n_graphs), valid=lambda v: v is not None)
+
+
+def num_graphs(batch, n):
+    """batch.max() + 1: known_num_graphs, else the (cached) batch layout's one read."""
+    G = known_num_graphs(batch)
+    if G is None:
+        layout = cached_batch_layout(batch, n)
+        # the layout counts graphs from the last entry: the maximum only for a sorted batch
+        G = layout.n_graphs if not layout.unsorted else int(batch.max()) + 1
+        note_num_graphs(batch, G)
+    return G
+
+
+def voxel_keys(pos, batch, size, start, end):
+    """key [N] int64 of mp_voxel_keys_f32: pos [N, D] float32 (D <= 8), batch [N]
+    int64 or None, size / start / end: float32 device tensors of D (+ 1 with a
+    batch) entries.  No host read."""
+    _lib.require_device(pos, batch, size, start, end)
+    if pos.dtype != torch.float32:
+        raise TypeError("mi355_mp: voxel_grid positions must be float32 (got %s)" % pos.dtype)
+    pos = pos.detach()
+    pos = pos.view(-1, 1) if pos.dim() == 1 else pos
+    if pos.dim() != 2:
+        raise ValueError("mi355_mp: pos must be [N] or [N, D]")
+    if pos.stride(1) != 1 or pos.stride(0) < pos.shape[1]:
+        pos = pos.contiguous()
+    n, D = pos.shape
+    Dt = D + (0 if batch is None else 1)
+    if D > 8:
+        raise ValueError("mi355_mp: voxel_grid takes at most 8 position columns (got %d)" % D)
+    if batch is not None:
+        if batch.dtype != torch.int64 or batch.dim() != 1 or batch.shape[0] != n:
+            raise ValueError("mi355_mp: batch must be int64 [%d] (got %s %s)" % (n, batch.dtype, tuple(batch.shape)))
+        batch = batch.contiguous()
+    geo = []
+    for name, t in (("size", size), ("start", start), ("end", end)):
+        if t.dtype != torch.float32 or t.dim() != 1 or t.numel() != Dt:
+            raise ValueError("mi355_mp: %s must be float32 [%d] (got %s %s)" % (name, Dt, t.dtype, tuple(t.shape)))
+        geo.append(t.contiguous())
+    key = torch.empty(n, dtype=torch.int64, device=pos.device)
+    _lib.check(_lib.load().mp_voxel_keys_f32(pos.data_ptr(), pos.stride(0), n, D, _lib.ptr(batch), geo[0].data_ptr(),
+                                             geo[1].data_ptr(), geo[2].data_ptr(), key.data_ptr(), _lib.nbytes(key),
+                                             _lib.stream_ptr(pos.device)), "mp_voxel_keys_f32")
+    return key
+
+
+class ClusterSelection(object):
+    """What mp_cluster_build leaves on the device: inv [n], the cluster CSR rowptr
+    [n + 1] / member [n] (int32), perm (sized n, its first M entries valid) and
+    counts (int64[4]: M, then pool_edges' output edges and bad edge ends).  M,
+    n_edges_out: filled by cluster_read_counts."""
+    __slots__ = ("inv", "rowptr", "member", "perm", "counts", "n", "M", "n_edges_out")
+
+    def __init__(self, inv, rowptr, member, perm, counts, n):
+        self.inv, self.rowptr, self.member, self.perm, self.counts, self.n = inv, rowptr, member, perm, counts, n
+        self.M = self.n_edges_out = None
+
+    def member_counts(self, M):
+        """float32 [M, 1]: the number of nodes of every cluster."""
+        return (self.rowptr[1:M + 1] - self.rowptr[:M]).to(torch.float32).view(-1, 1)
+
+
+def cluster_build(key):
+    """ClusterSelection of any int64 key vector (mp_cluster_build): one stable
+    sort of (key, node index), the run heads and their scan.  No host read."""
+    _lib.require_device(key)
+    if key.dtype != torch.int64 or key.dim() != 1:
+        raise ValueError("mi355_mp: cluster must be a 1-D int64 tensor (got %s %s)" % (key.dtype, tuple(key.shape)))
+    lib = _lib.load()
+    key = key.contiguous()
+    n = key.numel()
+    dev = key.device
+    inv = torch.empty(n, dtype=torch.int64, device=dev)
+    rowptr = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    member = torch.empty(n, dtype=torch.int32, device=dev)
+    perm = torch.empty(n, dtype=torch.int64, device=dev)
+    counts = torch.zeros(4, dtype=torch.int64, device=dev)
+    wsb = lib.mp_cluster_build_workspace(n)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    _lib.check(lib.mp_cluster_build(key.data_ptr(), n, inv.data_ptr(), _lib.nbytes(inv), rowptr.data_ptr(),
+                                    _lib.nbytes(rowptr), member.data_ptr(), _lib.nbytes(member), perm.data_ptr(),
+                                    _lib.nbytes(perm), counts.data_ptr(), ws.data_ptr(), wsb, _lib.stream_ptr(dev)),
+               "mp_cluster_build")
+    return ClusterSelection(inv, rowptr, member, perm, counts, n)
+
+
+def cluster_read_counts(sel, n=None):
+    """The one host read after everything has been enqueued: (M, E', bad edge
+    ends), kept on sel.  Raises IndexError when pool_edges met an edge end
+    outside [0, n), as upstream's cluster[edge_index] does."""
+    if sel.M is None:
+        M, kept, bad, _ = sel.counts.tolist()
+        if bad:
+            raise IndexError("pool_edge: %d edge ends lie outside [0, %d)" % (bad, sel.n if n is None else n))
+        sel.M, sel.n_edges_out = M, kept
+    return sel.M, sel.n_edges_out, 0
+
+
+class _ClusterReduce(torch.autograd.Function):
+    """mp_cluster_reduce_f32: (x_out, arg, pos_out, batch_out) at their upper bound
+    of n rows, the first M valid.  Backward: the max routes every output gradient
+    to its arg row (mp_scatter_arg_backward_f32); the means gather g / count by
+    inv (gather_rows)."""
+
+    @staticmethod
+    def forward(ctx, x, pos, sel, reduce, batch, pyg_mask):
+        lib = _lib.load()
+        n = sel.n
+        dev = sel.inv.device
+        is_max = reduce == "max"
+        F = Dp = 0
+        x_out = arg = pos_out = batch_out = keep = None
+        need_mask_grad = False
+        if x is not None:
+            x = _pool_rows(x, "x")
+            F = x.shape[1]
+            x_out = torch.empty((n, F), dtype=torch.float32, device=dev)
+            arg = torch.empty((n, F), dtype=torch.int64, device=dev) if is_max else None
+            need_mask_grad = pyg_mask and is_max and ctx.needs_input_grad[0]
+        if pos is not None:
+            pos = _pool_rows(pos, "pos")
+            Dp = pos.shape[1]
+            pos_out = torch.empty((n, Dp), dtype=torch.float32, device=dev)
+        if batch is not None:
+            batch_out = torch.empty(n, dtype=torch.int64, device=dev)
+        flags = _lib.MP_FLAG_PYG_MASK if (pyg_mask and is_max and not need_mask_grad) else 0
+        if n:
+            _lib.check(lib.mp_cluster_reduce_f32(
+                _lib.ptr(x), x.stride(0) if F else 0, F, _lib.MP_REDUCE[reduce], flags, sel.rowptr.data_ptr(),
+                sel.member.data_ptr(), sel.counts.data_ptr(), n, _lib.ptr(x_out), F, _lib.nbytes(x_out),
+                _lib.ptr(arg), _lib.nbytes(arg), _lib.ptr(pos), pos.stride(0) if Dp else 0, Dp, _lib.ptr(pos_out),
+                _lib.nbytes(pos_out), _lib.ptr(batch), sel.perm.data_ptr(), _lib.ptr(batch_out),
+                _lib.nbytes(batch_out), _lib.stream_ptr(dev)), "mp_cluster_reduce_f32")
+        if need_mask_grad:
+            keep = ~(x_out < -10000)
+            x_out = x_out.masked_fill(~keep, 0.0)
+        ctx.sel, ctx.is_max, ctx.F, ctx.Dp = sel, is_max, F, Dp
+        ctx.save_for_backward(arg, keep)
+        # an output follows its own input only: pooled positions of constant positions stay constant
+        # (Cartesian pseudo-coordinates of them must not ask SplineConv for a pseudo gradient)
+        const = [arg, batch_out, None if ctx.needs_input_grad[0] else x_out,
+                 None if ctx.needs_input_grad[1] else pos_out]
+        ctx.mark_non_differentiable(*[t for t in const if t is not None])
+        return x_out, arg, pos_out, batch_out
+
+    @staticmethod
+    def backward(ctx, g_x, _g_arg, g_pos, _g_batch):
+        sel = ctx.sel
+        arg, keep = ctx.saved_tensors
+        n = sel.n
+        M = cluster_read_counts(sel)[0]
+        gx = gp = None
+        cnt = sel.member_counts(M)
+        if ctx.F and ctx.needs_input_grad[0] and g_x is not None:
+            g = g_x[:M]
+            if keep is not None:
+                g = g * keep[:M]
+            g = g.contiguous()
+            if ctx.is_max:
+                gx = torch.zeros((n, ctx.F), dtype=torch.float32, device=g.device)
+                _lib.check(_lib.load().mp_scatter_arg_backward_f32(g.data_ptr(), arg.data_ptr(), M, ctx.F, n,
+                                                                   gx.data_ptr(), ctx.F, _lib.stream_ptr(g.device)),
+                           "mp_scatter_arg_backward_f32")
+            else:
+                gx = gather_rows(g / cnt, sel.inv)
+        if ctx.Dp and ctx.needs_input_grad[1] and g_pos is not None:
+            gp = gather_rows(g_pos[:M] / cnt, sel.inv)
+        return gx, gp, None, None, None, None
+
+
+def cluster_reduce(sel, x=None, reduce="max", pos=None, batch=None, pyg_mask=True):
+    """(x_out, arg, pos_out, batch_out) of the clusters of sel, each sized n with
+    its first M rows valid (slice after cluster_read_counts): x_out = the max
+    (arg = the winning node, the lowest index among equals; pyg_mask: out <
+    -10000 := 0) or the mean of x over every cluster, pos_out = the mean of pos,
+    batch_out = batch[perm].  float32 only; differentiable in x and pos.  No
+    host read."""
+    if reduce not in ("max", "mean"):
+        raise ValueError("mi355_mp: cluster_reduce takes 'max' or 'mean' (got %r)" % (reduce,))
+    _lib.require_device(sel.inv, x, pos, batch)
+    for name, t in (("x", x), ("pos", pos)):
+        if t is not None and t.shape[0] != sel.n:
+            raise ValueError("mi355_mp: %s has %d rows, the clustering %d nodes" % (name, t.shape[0], sel.n))
+    if batch is not None:
+        if batch.dtype != torch.int64 or batch.dim() != 1 or batch.shape[0] != sel.n:
+            raise ValueError("mi355_mp: batch must be int64 [%d]" % sel.n)
+        batch = batch.contiguous()
+    return _ClusterReduce.apply(x, pos, sel, reduce, batch, pyg_mask)
+
+
+class EdgePooling(object):
+    """What mp_cluster_edges leaves on the device: out [2, E] (first E' columns
+    valid), edge_slot [E] (the output position of every original edge, -1 =
+    dropped) and the duplicates of every output edge seg_ptr [E + 1] / seg_edge
+    [E] (int32, ascending original position)."""
+    __slots__ = ("out", "edge_slot", "seg_ptr", "seg_edge", "n_edges")
+
+    def __init__(self, out, edge_slot, seg_ptr, seg_edge, n_edges):
+        self.out, self.edge_slot, self.seg_ptr, self.seg_edge, self.n_edges = out, edge_slot, seg_ptr, seg_edge, n_edges
+
+
+def pool_edges(edge_index, sel):
+    """pool_edge's index side against sel.inv (mp_cluster_edges): relabel, drop
+    the loops, sort the pairs and merge the duplicates; sel.counts[1] = output
+    edges, [2] = edge ends outside [0, n).  No host read."""
+    _lib.require_device(edge_index)
+    lib = _lib.load()
+    dev = edge_index.device
+    E = int(edge_index.shape[1])
+    row = edge_index[0].to(torch.int64).contiguous()
+    col = edge_index[1].to(torch.int64).contiguous()
+    out = torch.empty((2, E), dtype=torch.int64, device=dev)
+    slot = torch.empty(E, dtype=torch.int64, device=dev)
+    seg_ptr = torch.empty(E + 1, dtype=torch.int32, device=dev)
+    seg_edge = torch.empty(E, dtype=torch.int32, device=dev)
+    wsb = lib.mp_cluster_edges_workspace(E, sel.n)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    _lib.check(lib.mp_cluster_edges(row.data_ptr(), col.data_ptr(), E, sel.inv.data_ptr(), sel.n,
+                                    sel.counts.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), slot.data_ptr(),
+                                    E * 8, seg_ptr.data_ptr(), _lib.nbytes(seg_ptr), seg_edge.data_ptr(),
+                                    _lib.nbytes(seg_edge), ws.data_ptr(), wsb, _lib.stream_ptr(dev)),
+               "mp_cluster_edges")
+    sel.M = sel.n_edges_out = None
+    return EdgePooling(out, slot, seg_ptr, seg_edge, E)
+
+
+class _PoolEdgeAttr(torch.autograd.Function):
+    """attr_out[k] = the sum of attr over the duplicates of output edge k in
+    ascending original position (mp_cluster_edge_attr_f32), sized E rows; the
+    backward hands every kept edge its output edge's gradient
+    (mp_cluster_edge_attr_bwd_f32: a gather by edge_slot, 0 for a dropped edge)."""
+
+    @staticmethod
+    def forward(ctx, attr, ep, sel):
+        flat = attr.reshape(attr.shape[0], -1)
+        if flat.stride(1) != 1 or flat.stride(0) < max(flat.shape[1], 1):
+            flat = flat.contiguous()
+        E, A = flat.shape
+        out = torch.empty((E, A), dtype=torch.float32, device=attr.device)
+        if E and A:
+            _lib.check(_lib.load().mp_cluster_edge_attr_f32(flat.data_ptr(), flat.stride(0), A, ep.seg_ptr.data_ptr(),
+                                                            ep.seg_edge.data_ptr(), sel.counts.data_ptr(), E,
+                                                            out.data_ptr(), A, _lib.nbytes(out),
+                                                            _lib.stream_ptr(attr.device)), "mp_cluster_edge_attr_f32")
+        ctx.ep, ctx.sel, ctx.shape = ep, sel, attr.shape
+        return out.view((E,) + tuple(attr.shape[1:]))
+
+    @staticmethod
+    def backward(ctx, g):
+        E = ctx.shape[0]
+        kept = cluster_read_counts(ctx.sel)[1]
+        g = g.reshape(E, -1).contiguous()
+        A = g.shape[1]
+        ga = torch.empty((E, A), dtype=torch.float32, device=g.device)
+        if E and A:
+            _lib.check(_lib.load().mp_cluster_edge_attr_bwd_f32(g.data_ptr(), A, ctx.ep.edge_slot.data_ptr(), E, A,
+                                                                kept, ga.data_ptr(), A, _lib.nbytes(ga),
+                                                                _lib.stream_ptr(g.device)),
+                       "mp_cluster_edge_attr_bwd_f32")
+        return ga.view(ctx.shape), None, None
+
+
+def pool_edge_attr_sum(edge_attr, ep, sel):
+    """The coalesced edge attributes of pool_edges' output edges, sized E rows
+    (slice to E' after cluster_read_counts).  float32 of any trailing shape;
+    every other dtype is rejected (torch_sparse sums them with scatter_add, the
+    native kernel is float32 only).  Differentiable.  No host read."""
+    _lib.require_device(edge_attr)
+    if edge_attr.dtype != torch.float32:
+        raise TypeError("mi355_mp: pool_edge sums float32 edge attributes only (got %s)" % edge_attr.dtype)
+    if edge_attr.shape[0] != ep.n_edges:
+        raise ValueError("mi355_mp: edge_attr has %d rows, edge_index %d edges" % (edge_attr.shape[0], ep.n_edges))
+    if edge_attr.numel() == 0:
+        return edge_attr          # no edges (or no columns): the empty selection, as upstream's edge_attr[mask]
+    return _PoolEdgeAttr.apply(edge_attr, ep, sel)
