@@ -18,10 +18,9 @@
 // downstream of a sort is sized by its upper bound (n or E) and reads the count.
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_scan.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
 
-#include "mp_common.h"
+#include "mp_workspace.h"
 
 namespace mp {
 
@@ -31,12 +30,6 @@ constexpr int kClusterBlock = 256;
 // the chip (4 waves per workgroup, 8 per SIMD), and gridDim.x * blockDim.x
 // stays far below 2^32 for any n < 2^31
 constexpr int kClusterMaxBlocks = 2048;
-
-static inline int cluster_group_lanes(int64_t elems) {
-  int gl = 1;
-  while (gl < 64 && gl < elems) gl <<= 1;
-  return gl;
-}
 
 static inline unsigned cluster_row_blocks(int64_t rows, int gl) {
   const int64_t waves = ceil_div(rows > 0 ? rows : 1, 64 / gl);
@@ -120,24 +113,24 @@ __global__ __launch_bounds__(kClusterBlock) void k_cluster_emit(const int64_t* _
   }
 }
 
-static hipError_t cluster_sort_bytes(int64_t n, size_t* bytes) {
-  *bytes = 0;
-  return rocprim::radix_sort_pairs((void*)nullptr, *bytes, (const int64_t*)nullptr, (int64_t*)nullptr,
-                                   rocprim::counting_iterator<int32_t>(0), (int32_t*)nullptr,
-                                   (size_t)(n > 0 ? n : 1), 0u, 64u, (hipStream_t)0, false);
-}
-
-static hipError_t cluster_scan_bytes(int64_t n, size_t* bytes) {
-  *bytes = 0;
-  HeadIter it(rocprim::counting_iterator<int>(0), RunHead{nullptr});
-  return rocprim::inclusive_scan((void*)nullptr, *bytes, it, (int32_t*)nullptr, (size_t)(n > 0 ? n : 1),
-                                 rocprim::plus<int>(), (hipStream_t)0, false);
-}
-
-static size_t cluster_build_fixed(int64_t n) {
+// temp bytes of mp_cluster_build's sort and of its scan
+static hipError_t cluster_build_temp(int64_t n, size_t* sort_b, size_t* scan_b) {
   const size_t nn = (size_t)(n > 0 ? n : 1);
-  return align_up(nn * 8, 256) + align_up(nn * 4, 256);
+  HeadIter it(rocprim::counting_iterator<int>(0), RunHead{nullptr});
+  const hipError_t e = rocprim::radix_sort_pairs((void*)nullptr, *sort_b, (const int64_t*)nullptr, (int64_t*)nullptr,
+                                                 rocprim::counting_iterator<int32_t>(0), (int32_t*)nullptr, nn, 0u,
+                                                 64u, (hipStream_t)0, false);
+  const hipError_t e2 = rocprim::inclusive_scan((void*)nullptr, *scan_b, it, (int32_t*)nullptr, nn,
+                                                rocprim::plus<int>(), (hipStream_t)0, false);
+  return e != hipSuccess ? e : e2;
 }
+
+// mp_cluster_build's workspace, then the temp the sort and the scan share (the larger of the two)
+struct ClusterBuildWs : Carver {
+  int64_t n;
+  int64_t* ks = take<int64_t>(n);
+  int32_t* cid = take<int32_t>(n);
+};
 
 // ---- per-cluster reduce ----------------------------------------------------------
 
@@ -265,24 +258,25 @@ static int cluster_key_log2(int64_t n) {
   return L;  // <= 31 for n < 2^31
 }
 
-static hipError_t cluster_edge_sort_bytes(int64_t E, unsigned bits, size_t* bytes) {
-  *bytes = 0;
-  return rocprim::radix_sort_pairs((void*)nullptr, *bytes, (const uint64_t*)nullptr, (uint64_t*)nullptr,
-                                   rocprim::counting_iterator<int32_t>(0), (int32_t*)nullptr,
-                                   (size_t)(E > 0 ? E : 1), 0u, bits, (hipStream_t)0, false);
-}
-
-static hipError_t cluster_edge_scan_bytes(int64_t E, size_t* bytes) {
-  *bytes = 0;
-  EdgeHeadIter it(rocprim::counting_iterator<int>(0), EdgeRunHead{nullptr, 0});
-  return rocprim::inclusive_scan((void*)nullptr, *bytes, it, (int32_t*)nullptr, (size_t)(E > 0 ? E : 1),
-                                 rocprim::plus<int>(), (hipStream_t)0, false);
-}
-
-static size_t cluster_edges_fixed(int64_t E) {
+// temp bytes of mp_cluster_edges' sort and of its scan
+static hipError_t cluster_edges_temp(int64_t E, unsigned bits, size_t* sort_b, size_t* scan_b) {
   const size_t ee = (size_t)(E > 0 ? E : 1);
-  return 2 * align_up(ee * 8, 256) + align_up(ee * 4, 256);
+  EdgeHeadIter it(rocprim::counting_iterator<int>(0), EdgeRunHead{nullptr, 0});
+  const hipError_t e = rocprim::radix_sort_pairs((void*)nullptr, *sort_b, (const uint64_t*)nullptr, (uint64_t*)nullptr,
+                                                 rocprim::counting_iterator<int32_t>(0), (int32_t*)nullptr, ee, 0u,
+                                                 bits, (hipStream_t)0, false);
+  const hipError_t e2 = rocprim::inclusive_scan((void*)nullptr, *scan_b, it, (int32_t*)nullptr, ee,
+                                                rocprim::plus<int>(), (hipStream_t)0, false);
+  return e != hipSuccess ? e : e2;
 }
+
+// mp_cluster_edges' workspace (slot1: output slot + 1), then the temp the sort and the scan share
+struct ClusterEdgesWs : Carver {
+  int64_t n_edges;
+  uint64_t* keys = take<uint64_t>(n_edges);
+  uint64_t* ks = take<uint64_t>(n_edges);
+  int32_t* slot1 = take<int32_t>(n_edges);
+};
 
 // attr_out[k, :] = ((0 + attr[e_0, :]) + attr[e_1, :]) + ... over the duplicates
 // of output edge k in ascending original position
@@ -361,9 +355,8 @@ int mp_voxel_keys_f32(const float* pos, int64_t ldp, int64_t n, int32_t D, const
 
 size_t mp_cluster_build_workspace(int64_t n) {
   size_t a = 0, b = 0;
-  (void)cluster_sort_bytes(n, &a);
-  (void)cluster_scan_bytes(n, &b);
-  return cluster_build_fixed(n) + align_up(a > b ? a : b, 256) + 256;
+  (void)cluster_build_temp(n, &a, &b);
+  return ClusterBuildWs{nullptr, n}.total(a > b ? a : b);
 }
 
 int mp_cluster_build(const int64_t* key, int64_t n, int64_t* inv, size_t inv_bytes, int32_t* rowptr,
@@ -383,7 +376,8 @@ int mp_cluster_build(const int64_t* key, int64_t n, int64_t* inv, size_t inv_byt
   MP_CHECK_EXTENT("mp_cluster_build", "rowptr", rowptr_bytes, (size_t)(n + 1) * sizeof(int32_t));
   MP_CHECK_EXTENT("mp_cluster_build", "member", member_bytes, (size_t)n * sizeof(int32_t));
   MP_CHECK_EXTENT("mp_cluster_build", "perm", perm_bytes, (size_t)n * sizeof(int64_t));
-  MP_CHECK_EXTENT("mp_cluster_build", "ws", ws_bytes, cluster_build_fixed(n) + 256);
+  const ClusterBuildWs w{ws, n};
+  MP_CHECK_EXTENT("mp_cluster_build", "ws", ws_bytes, w.total(0));
   hipStream_t s = as_stream(stream);
   if (n == 0) {
     MP_CHECK_HIP(hipMemsetAsync(counts, 0, sizeof(int64_t), s));
@@ -391,22 +385,15 @@ int mp_cluster_build(const int64_t* key, int64_t n, int64_t* inv, size_t inv_byt
     return MP_OK;
   }
   size_t sort_b = 0, scan_b = 0;
-  MP_CHECK_HIP(cluster_sort_bytes(n, &sort_b));
-  MP_CHECK_HIP(cluster_scan_bytes(n, &scan_b));
-  const size_t tmp_b = sort_b > scan_b ? sort_b : scan_b;
-  MP_CHECK_EXTENT("mp_cluster_build", "ws", ws_bytes, cluster_build_fixed(n) + align_up(tmp_b, 256) + 256);
-  char* p = (char*)ws;
-  int64_t* ks = (int64_t*)p;
-  p += align_up((size_t)n * 8, 256);
-  int32_t* cid = (int32_t*)p;
-  p += align_up((size_t)n * 4, 256);
-  void* tmp = p;
-  MP_CHECK_HIP(rocprim::radix_sort_pairs(tmp, sort_b, key, ks, rocprim::counting_iterator<int32_t>(0), member,
+  const hipError_t size_query = cluster_build_temp(n, &sort_b, &scan_b);
+  MP_CHECK_EXTENT("mp_cluster_build", "ws", ws_bytes, w.total(std::max(sort_b, scan_b)));
+  MP_CHECK_HIP(size_query);
+  MP_CHECK_HIP(rocprim::radix_sort_pairs(w.rest(), sort_b, key, w.ks, rocprim::counting_iterator<int32_t>(0), member,
                                          (size_t)n, 0u, 64u, s, false));
-  HeadIter heads(rocprim::counting_iterator<int>(0), RunHead{ks});
-  MP_CHECK_HIP(rocprim::inclusive_scan(tmp, scan_b, heads, cid, (size_t)n, rocprim::plus<int>(), s, false));
-  k_cluster_emit<<<(unsigned)ceil_div(n, kClusterBlock), kClusterBlock, 0, s>>>(ks, member, cid, n, inv, rowptr, perm,
-                                                                                counts);
+  HeadIter heads(rocprim::counting_iterator<int>(0), RunHead{w.ks});
+  MP_CHECK_HIP(rocprim::inclusive_scan(w.rest(), scan_b, heads, w.cid, (size_t)n, rocprim::plus<int>(), s, false));
+  k_cluster_emit<<<(unsigned)ceil_div(n, kClusterBlock), kClusterBlock, 0, s>>>(w.ks, member, w.cid, n, inv, rowptr,
+                                                                                perm, counts);
   MP_CHECK_LAUNCH();
   return MP_OK;
 }
@@ -443,7 +430,7 @@ int mp_cluster_reduce_f32(const float* x, int64_t ldx, int32_t F, int32_t reduce
   if (arg) MP_CHECK_EXTENT("mp_cluster_reduce_f32", "arg", arg_bytes, (size_t)n * (size_t)F * sizeof(int64_t));
   if (Dp > 0) MP_CHECK_EXTENT("mp_cluster_reduce_f32", "pos_out", pos_out_bytes, (size_t)n * (size_t)Dp * sizeof(float));
   if (batch_out) MP_CHECK_EXTENT("mp_cluster_reduce_f32", "batch_out", batch_out_bytes, (size_t)n * sizeof(int64_t));
-  const int gl = cluster_group_lanes(F > Dp ? F : Dp);
+  const int gl = group_lanes(F > Dp ? F : Dp);
   k_cluster_reduce<<<cluster_row_blocks(n, gl), kClusterBlock, 0, as_stream(stream)>>>(
       x, ldx, F, reduce == MP_REDUCE_MAX, (flags & MP_FLAG_PYG_MASK) ? 1 : 0, rowptr, member, counts, n, x_out, ldo,
       reduce == MP_REDUCE_MAX ? arg : nullptr, pos, ldp, Dp, pos_out, Dp, batch, perm, batch_out, gl);
@@ -454,9 +441,8 @@ int mp_cluster_reduce_f32(const float* x, int64_t ldx, int32_t F, int32_t reduce
 size_t mp_cluster_edges_workspace(int64_t n_edges, int64_t n_nodes) {
   size_t a = 0, b = 0;
   const unsigned bits = 2u * (unsigned)cluster_key_log2(n_nodes > 0 ? n_nodes : 1) + 1u;
-  (void)cluster_edge_sort_bytes(n_edges, bits, &a);
-  (void)cluster_edge_scan_bytes(n_edges, &b);
-  return cluster_edges_fixed(n_edges) + align_up(a > b ? a : b, 256) + 256;
+  (void)cluster_edges_temp(n_edges, bits, &a, &b);
+  return ClusterEdgesWs{nullptr, n_edges}.total(a > b ? a : b);
 }
 
 int mp_cluster_edges(const int64_t* row, const int64_t* col, int64_t n_edges, const int64_t* inv, int64_t n_nodes,
@@ -481,7 +467,8 @@ int mp_cluster_edges(const int64_t* row, const int64_t* col, int64_t n_edges, co
   MP_CHECK_EXTENT("mp_cluster_edges", "out_row / out_col / edge_slot", out_bytes, (size_t)n_edges * sizeof(int64_t));
   MP_CHECK_EXTENT("mp_cluster_edges", "seg_ptr", seg_ptr_bytes, (size_t)(n_edges + 1) * sizeof(int32_t));
   MP_CHECK_EXTENT("mp_cluster_edges", "seg_edge", seg_edge_bytes, (size_t)n_edges * sizeof(int32_t));
-  MP_CHECK_EXTENT("mp_cluster_edges", "ws", ws_bytes, cluster_edges_fixed(n_edges) + 256);
+  const ClusterEdgesWs w{ws, n_edges};
+  MP_CHECK_EXTENT("mp_cluster_edges", "ws", ws_bytes, w.total(0));
   hipStream_t s = as_stream(stream);
   if (n_edges == 0) {
     MP_CHECK_HIP(hipMemsetAsync(counts + 1, 0, 2 * sizeof(int64_t), s));
@@ -492,29 +479,21 @@ int mp_cluster_edges(const int64_t* row, const int64_t* col, int64_t n_edges, co
   const uint64_t sentinel = (uint64_t)1 << (2 * L);  // above every a * M + b < n^2 <= 2^(2L)
   const unsigned bits = 2u * (unsigned)L + 1u;
   size_t sort_b = 0, scan_b = 0;
-  MP_CHECK_HIP(cluster_edge_sort_bytes(n_edges, bits, &sort_b));
-  MP_CHECK_HIP(cluster_edge_scan_bytes(n_edges, &scan_b));
-  const size_t tmp_b = sort_b > scan_b ? sort_b : scan_b;
-  MP_CHECK_EXTENT("mp_cluster_edges", "ws", ws_bytes, cluster_edges_fixed(n_edges) + align_up(tmp_b, 256) + 256);
+  const hipError_t size_query = cluster_edges_temp(n_edges, bits, &sort_b, &scan_b);
+  MP_CHECK_EXTENT("mp_cluster_edges", "ws", ws_bytes, w.total(std::max(sort_b, scan_b)));
+  MP_CHECK_HIP(size_query);
   MP_CHECK_HIP(hipMemsetAsync(counts + 1, 0, 2 * sizeof(int64_t), s));
-  char* p = (char*)ws;
-  uint64_t* keys = (uint64_t*)p;
-  p += align_up((size_t)n_edges * 8, 256);
-  uint64_t* ks = (uint64_t*)p;
-  p += align_up((size_t)n_edges * 8, 256);
-  int32_t* slot1 = (int32_t*)p;
-  p += align_up((size_t)n_edges * 4, 256);
-  void* tmp = p;
   const unsigned blocks = (unsigned)ceil_div(n_edges, kClusterBlock);
-  k_cluster_edge_keys<<<blocks, kClusterBlock, 0, s>>>(row, col, n_edges, inv, n_nodes, sentinel, keys,
+  k_cluster_edge_keys<<<blocks, kClusterBlock, 0, s>>>(row, col, n_edges, inv, n_nodes, sentinel, w.keys,
                                                        reinterpret_cast<unsigned long long*>(counts));
   MP_CHECK_LAUNCH();
-  MP_CHECK_HIP(rocprim::radix_sort_pairs(tmp, sort_b, (const uint64_t*)keys, ks,
+  MP_CHECK_HIP(rocprim::radix_sort_pairs(w.rest(), sort_b, (const uint64_t*)w.keys, w.ks,
                                          rocprim::counting_iterator<int32_t>(0), seg_edge, (size_t)n_edges, 0u, bits,
                                          s, false));
-  EdgeHeadIter heads(rocprim::counting_iterator<int>(0), EdgeRunHead{ks, sentinel});
-  MP_CHECK_HIP(rocprim::inclusive_scan(tmp, scan_b, heads, slot1, (size_t)n_edges, rocprim::plus<int>(), s, false));
-  k_cluster_edge_emit<<<blocks, kClusterBlock, 0, s>>>(ks, seg_edge, slot1, n_edges, n_nodes, sentinel, out_row,
+  EdgeHeadIter heads(rocprim::counting_iterator<int>(0), EdgeRunHead{w.ks, sentinel});
+  MP_CHECK_HIP(rocprim::inclusive_scan(w.rest(), scan_b, heads, w.slot1, (size_t)n_edges, rocprim::plus<int>(), s,
+                                       false));
+  k_cluster_edge_emit<<<blocks, kClusterBlock, 0, s>>>(w.ks, seg_edge, w.slot1, n_edges, n_nodes, sentinel, out_row,
                                                        out_col, edge_slot, seg_ptr, counts);
   MP_CHECK_LAUNCH();
   return MP_OK;
@@ -537,7 +516,7 @@ int mp_cluster_edge_attr_f32(const float* attr, int64_t lda, int32_t A, const in
   MP_CHECK_ARG(out, "mp_cluster_edge_attr_f32: out is NULL");
   MP_CHECK_EXTENT("mp_cluster_edge_attr_f32", "out", out_bytes,
                   ((size_t)(n_edges - 1) * (size_t)ldo + (size_t)A) * sizeof(float));
-  const int gl = cluster_group_lanes(A);
+  const int gl = group_lanes(A);
   k_cluster_edge_attr<<<cluster_row_blocks(n_edges, gl), kClusterBlock, 0, as_stream(stream)>>>(
       attr, lda, A, seg_ptr, seg_edge, counts, n_edges, out, ldo, gl);
   MP_CHECK_LAUNCH();

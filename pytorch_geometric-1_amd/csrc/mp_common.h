@@ -66,6 +66,14 @@ static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; 
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// lane groups of the row kernels: gl (the power of two >= elems, at most 64)
+// lanes per row, 64 / gl rows per wave
+static inline int group_lanes(int64_t elems) {
+  int gl = 1;
+  while (gl < 64 && gl < elems) gl <<= 1;
+  return gl;
+}
+
 // Sum over aligned groups of `g` lanes (g a power of two <= 64, wave-uniform)
 // with DPP lane permutes (quad_perm, row_half_mirror, row_mirror) fused into
 // the adds; every lane of a group ends with the same value (each step adds a

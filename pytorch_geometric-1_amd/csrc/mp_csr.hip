@@ -8,10 +8,8 @@
 #include <stdarg.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
 
-#include "mp_common.h"
+#include "mp_workspace.h"
 
 namespace mp {
 
@@ -80,13 +78,19 @@ static unsigned bits_for(int64_t n_rows) {
   return b;
 }
 
-static size_t sort_temp_bytes(int64_t n_edges, int64_t n_rows) {
-  size_t bytes = 0;
-  (void)rocprim::radix_sort_pairs((void*)nullptr, bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                            (const int32_t*)nullptr, (int32_t*)nullptr, (size_t)n_edges, 0,
-                            bits_for(n_rows), (hipStream_t)0, false);
-  return bytes;
+static hipError_t sort_temp_bytes(int64_t n_edges, int64_t n_rows, size_t* bytes) {
+  return rocprim::radix_sort_pairs((void*)nullptr, *bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr,
+                                   (const int32_t*)nullptr, (int32_t*)nullptr, (size_t)n_edges, 0,
+                                   bits_for(n_rows), (hipStream_t)0, false);
 }
+
+// mp_csr_build's workspace: the keys, the edge ids and the sorted keys, then the sort's temp
+struct CsrBuildWs : Carver {
+  int64_t n_edges;
+  uint32_t* keys32 = take<uint32_t>(n_edges);
+  int32_t* vals = take<int32_t>(n_edges);
+  uint32_t* ks = take<uint32_t>(n_edges);
+};
 
 // ---------------------------------------------------------------------------
 // Schedule kernels
@@ -159,13 +163,17 @@ __global__ void k_split_flags(const int32_t* __restrict__ rowptr, const int32_t*
   flags[w] = f;
 }
 
-static size_t select_temp_bytes(int32_t n_waves) {
-  size_t bytes = 0;
+static hipError_t select_temp_bytes(int32_t n_waves, size_t* bytes) {
   rocprim::counting_iterator<int32_t> it(0);
-  (void)rocprim::select((void*)nullptr, bytes, it, (const uint8_t*)nullptr, (int32_t*)nullptr,
-                  (int32_t*)nullptr, (size_t)n_waves, (hipStream_t)0, false);
-  return bytes;
+  return rocprim::select((void*)nullptr, *bytes, it, (const uint8_t*)nullptr, (int32_t*)nullptr,
+                         (int32_t*)nullptr, (size_t)n_waves, (hipStream_t)0, false);
 }
+
+// mp_schedule_build's workspace: one flag per wave task, then the select's temp
+struct ScheduleWs : Carver {
+  int32_t n_waves;
+  uint8_t* flags = take<uint8_t>(n_waves);
+};
 
 }  // namespace mp
 
@@ -178,8 +186,9 @@ const char* mp_last_error(void) { return mp::g_err; }
 int mp_abi_version(void) { return MP_ABI_VERSION; }
 
 size_t mp_csr_build_workspace(int64_t n_edges, int64_t n_rows) {
-  size_t e4 = align_up((size_t)(n_edges > 0 ? n_edges : 1) * 4, 256);
-  return 3 * e4 + align_up(sort_temp_bytes(n_edges, n_rows), 256) + 256;
+  size_t sort_bytes = 0;
+  (void)sort_temp_bytes(n_edges, n_rows, &sort_bytes);
+  return CsrBuildWs{nullptr, n_edges}.total(sort_bytes);
 }
 
 int mp_csr_build(const int64_t* key, const int64_t* other, int64_t n_edges, int64_t n_rows,
@@ -191,28 +200,24 @@ int mp_csr_build(const int64_t* key, const int64_t* other, int64_t n_edges, int6
                "mp_csr_build: int32 CSR limits exceeded (E=%lld, N=%lld)", (long long)n_edges,
                (long long)n_rows);
   MP_CHECK_ARG(rowptr && bad && (n_edges == 0 || (key && col && eid)), "mp_csr_build: null pointer");
-  MP_CHECK_ARG(ws_bytes >= mp_csr_build_workspace(n_edges, n_rows), "mp_csr_build: workspace too small");
+  const CsrBuildWs w{ws, n_edges};
+  size_t sort_bytes = 0;
+  const hipError_t size_query = sort_temp_bytes(n_edges, n_rows, &sort_bytes);
+  MP_CHECK_ARG(ws_bytes >= w.total(sort_bytes), "mp_csr_build: workspace too small");
+  MP_CHECK_HIP(size_query);
   hipStream_t s = as_stream(stream);
   MP_CHECK_HIP(hipMemsetAsync(bad, 0, sizeof(int32_t), s));
   if (n_edges == 0) {
     MP_CHECK_HIP(hipMemsetAsync(rowptr, 0, (size_t)(n_rows + 1) * sizeof(int32_t), s));
     return MP_OK;
   }
-  char* p = (char*)ws;
-  size_t e4 = align_up((size_t)n_edges * 4, 256);
-  uint32_t* keys32 = (uint32_t*)p; p += e4;
-  int32_t* vals = (int32_t*)p; p += e4;
-  uint32_t* ks = (uint32_t*)p; p += e4;
-  size_t sort_bytes = sort_temp_bytes(n_edges, n_rows);
-  void* tmp = p;
-
   const int B = 256;
-  k_prepare_keys<<<ceil_div(n_edges, B), B, 0, s>>>(key, other, n_edges, n_rows, n_other, keys32,
-                                                    vals, bad);
+  k_prepare_keys<<<ceil_div(n_edges, B), B, 0, s>>>(key, other, n_edges, n_rows, n_other, w.keys32,
+                                                    w.vals, bad);
   MP_CHECK_LAUNCH();
-  MP_CHECK_HIP(rocprim::radix_sort_pairs(tmp, sort_bytes, keys32, ks, vals, eid, (size_t)n_edges, 0,
+  MP_CHECK_HIP(rocprim::radix_sort_pairs(w.rest(), sort_bytes, w.keys32, w.ks, w.vals, eid, (size_t)n_edges, 0,
                                          bits_for(n_rows), s, false));
-  k_rowptr<<<ceil_div(n_rows + 1, B), B, 0, s>>>(ks, n_edges, n_rows, rowptr);
+  k_rowptr<<<ceil_div(n_rows + 1, B), B, 0, s>>>(w.ks, n_edges, n_rows, rowptr);
   MP_CHECK_LAUNCH();
   k_gather_col<<<ceil_div(n_edges, B), B, 0, s>>>(other, eid, n_edges, col);
   MP_CHECK_LAUNCH();
@@ -226,8 +231,9 @@ int32_t mp_schedule_n_waves(int64_t n_rows, int64_t n_edges, int32_t chunk) {
 }
 
 size_t mp_schedule_workspace(int32_t n_waves) {
-  return align_up((size_t)(n_waves > 0 ? n_waves : 1), 256) +
-         align_up(select_temp_bytes(n_waves), 256) + 256;
+  size_t sel_bytes = 0;
+  (void)select_temp_bytes(n_waves, &sel_bytes);
+  return ScheduleWs{nullptr, n_waves}.total(sel_bytes);
 }
 
 int mp_schedule_build(const int32_t* rowptr, int64_t n_rows, int64_t n_edges, int32_t chunk,
@@ -240,19 +246,20 @@ int mp_schedule_build(const int32_t* rowptr, int64_t n_rows, int64_t n_edges, in
                "mp_schedule_build: null pointer");
   MP_CHECK_ARG(n_rows + n_edges < (int64_t)INT32_MAX, "mp_schedule_build: N+E exceeds int32");
   int32_t n_waves = mp_schedule_n_waves(n_rows, n_edges, chunk);
-  MP_CHECK_ARG(ws_bytes >= mp_schedule_workspace(n_waves), "mp_schedule_build: workspace too small");
+  const ScheduleWs w{ws, n_waves};
+  size_t sel_bytes = 0;
+  const hipError_t size_query = select_temp_bytes(n_waves, &sel_bytes);
+  MP_CHECK_ARG(ws_bytes >= w.total(sel_bytes), "mp_schedule_build: workspace too small");
+  MP_CHECK_HIP(size_query);
   hipStream_t s = as_stream(stream);
   const int B = 256;
   k_wave_row<<<ceil_div((int64_t)n_waves + 1, B), B, 0, s>>>(rowptr, n_rows, n_edges, chunk, snap,
                                                              n_waves, wave_row, wave_slot);
   MP_CHECK_LAUNCH();
-  uint8_t* flags = (uint8_t*)ws;
-  void* tmp = (char*)ws + align_up((size_t)n_waves, 256);
-  k_split_flags<<<ceil_div(n_waves, B), B, 0, s>>>(rowptr, wave_row, wave_slot, n_waves, flags);
+  k_split_flags<<<ceil_div(n_waves, B), B, 0, s>>>(rowptr, wave_row, wave_slot, n_waves, w.flags);
   MP_CHECK_LAUNCH();
-  size_t sel_bytes = select_temp_bytes(n_waves);
   rocprim::counting_iterator<int32_t> it(0);
-  MP_CHECK_HIP(rocprim::select(tmp, sel_bytes, it, flags, split_waves, n_split_dev, (size_t)n_waves, s,
+  MP_CHECK_HIP(rocprim::select(w.rest(), sel_bytes, it, w.flags, split_waves, n_split_dev, (size_t)n_waves, s,
                                false));
   return MP_OK;
 }

@@ -10,10 +10,7 @@
 // its weight comes from (pos[k]; -1 = fill value), and a node's loop takes
 // the largest loop position (atomicMax over int32 positions) -- the same
 // choice, deterministic.  Weights are then one gather (mp_gather_fill_f32).
-#include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
-
-#include "mp_common.h"
+#include "mp_workspace.h"
 
 namespace mp {
 
@@ -69,13 +66,13 @@ __global__ void k_gather_fill(const float* __restrict__ src, const int64_t* __re
   out[k] = p >= 0 ? src[p] : fill;
 }
 
-static size_t loop_select_bytes(int64_t n) {
-  size_t bytes = 0;
-  rocprim::counting_iterator<int64_t> it(0);
-  (void)rocprim::select((void*)nullptr, bytes, it, (const uint8_t*)nullptr, (int64_t*)nullptr,
-                        (unsigned long long*)nullptr, (size_t)(n > 0 ? n : 1), (hipStream_t)0, false);
-  return bytes;
-}
+// mp_self_loops' workspace (last: a node's last loop position), then the select's temp
+struct SelfLoopsWs : Carver {
+  int64_t n_edges, n_nodes;
+  uint8_t* keep = take<uint8_t>(n_edges);
+  int32_t* last = take<int32_t>(n_nodes);
+  unsigned long long* n_sel = take<unsigned long long>(1);
+};
 
 }  // namespace mp
 
@@ -99,9 +96,9 @@ int mp_self_loop_count(const int64_t* row, const int64_t* col, int64_t n_edges, 
 }
 
 size_t mp_self_loops_workspace(int64_t n_edges, int64_t n_nodes) {
-  const size_t e = (size_t)(n_edges > 0 ? n_edges : 1);
-  const size_t n = (size_t)(n_nodes > 0 ? n_nodes : 1);
-  return align_up(e, 256) + align_up(n * 4, 256) + align_up(8, 256) + align_up(loop_select_bytes(n_edges), 256) + 256;
+  size_t sel_bytes = 0;
+  (void)select_positions_bytes(n_edges, &sel_bytes);
+  return SelfLoopsWs{nullptr, n_edges, n_nodes}.total(sel_bytes);
 }
 
 int mp_self_loops(const int64_t* row, const int64_t* col, int64_t n_edges, int64_t n_nodes, int32_t mode,
@@ -119,31 +116,26 @@ int mp_self_loops(const int64_t* row, const int64_t* col, int64_t n_edges, int64
   MP_CHECK_ARG(n_edges == 0 || (row && col), "mp_self_loops: null input");
   MP_CHECK_ARG(mode == MP_LOOPS_ADD || out_pos || n_kept == 0 || n_kept == n_edges,
                "mp_self_loops: out_pos is needed as the compaction buffer");
-  MP_CHECK_ARG(ws && ws_bytes >= mp_self_loops_workspace(n_edges, n_nodes), "mp_self_loops: workspace too small");
+  const SelfLoopsWs w{ws, n_edges, n_nodes};
+  size_t sel_bytes = 0;
+  const hipError_t size_query = select_positions_bytes(n_edges, &sel_bytes);
+  MP_CHECK_ARG(ws && ws_bytes >= w.total(sel_bytes), "mp_self_loops: workspace too small");
   hipStream_t s = as_stream(stream);
   if (n_out == 0) return MP_OK;
-  char* p = (char*)ws;
-  uint8_t* keep = (uint8_t*)p;
-  p += align_up((size_t)(n_edges > 0 ? n_edges : 1), 256);
-  int32_t* last = (int32_t*)p;
-  p += align_up((size_t)(n_nodes > 0 ? n_nodes : 1) * 4, 256);
-  unsigned long long* n_sel = (unsigned long long*)p;
-  p += align_up(8, 256);
-  void* tmp = p;
+  MP_CHECK_HIP(size_query);
   const int B = 256;
   const bool remaining = mode == MP_LOOPS_ADD_REMAINING;
   const bool identity = mode == MP_LOOPS_ADD || n_kept == n_edges;
-  if (remaining && n_nodes > 0) MP_CHECK_HIP(hipMemsetAsync(last, 0xff, (size_t)n_nodes * 4, s));  // -1
+  if (remaining && n_nodes > 0) MP_CHECK_HIP(hipMemsetAsync(w.last, 0xff, (size_t)n_nodes * 4, s));  // -1
   if (n_edges > 0 && (remaining || !identity)) {
-    k_loop_flags<<<ceil_div(n_edges, B), B, 0, s>>>(row, col, n_edges, n_nodes, keep, remaining ? last : nullptr);
+    k_loop_flags<<<ceil_div(n_edges, B), B, 0, s>>>(row, col, n_edges, n_nodes, w.keep, remaining ? w.last : nullptr);
     MP_CHECK_LAUNCH();
   }
   if (!identity) {
-    size_t sel_bytes = loop_select_bytes(n_edges);
     rocprim::counting_iterator<int64_t> it(0);
-    MP_CHECK_HIP(rocprim::select(tmp, sel_bytes, it, keep, out_pos, n_sel, (size_t)n_edges, s, false));
+    MP_CHECK_HIP(rocprim::select(w.rest(), sel_bytes, it, w.keep, out_pos, w.n_sel, (size_t)n_edges, s, false));
   }
-  k_loop_emit<<<ceil_div(n_out, B), B, 0, s>>>(row, col, n_kept, n_loops, remaining ? last : nullptr, out_row,
+  k_loop_emit<<<ceil_div(n_out, B), B, 0, s>>>(row, col, n_kept, n_loops, remaining ? w.last : nullptr, out_row,
                                                out_col, out_pos, identity);
   MP_CHECK_LAUNCH();
   return MP_OK;

@@ -17,22 +17,13 @@
 // counters and the integer maximum documented in the header.
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
-#include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
 
-#include "mp_common.h"
+#include "mp_workspace.h"
 
 namespace mp {
 
 constexpr int kPoolBlock = 256;
 constexpr int kScoreBwdMaxParts = 512;
-
-// ---- lane groups: gl (a power of two <= 64) lanes per row, 64 / gl rows per wave
-static inline int pool_group_lanes(int64_t elems) {
-  int gl = 1;
-  while (gl < 64 && gl < elems) gl <<= 1;
-  return gl;
-}
 
 static inline unsigned pool_row_blocks(int64_t rows, int gl) {
   const int64_t waves = ceil_div(rows, 64 / gl);
@@ -349,7 +340,6 @@ __global__ void k_topk_sort_emit(const uint64_t* __restrict__ sorted, int64_t n,
 
 static hipError_t topk_sort_bytes(int64_t n, int64_t G, size_t* bytes) {
   const size_t size = (size_t)(n > 0 ? n : 1);
-  *bytes = 0;
   if (G == 1)
     return rocprim::radix_sort_keys_desc((void*)nullptr, *bytes, (uint64_t*)nullptr, (uint64_t*)nullptr, size, 0u,
                                          64u, (hipStream_t)0, false);
@@ -358,12 +348,25 @@ static hipError_t topk_sort_bytes(int64_t n, int64_t G, size_t* bytes) {
                                                  64u, (hipStream_t)0, false);
 }
 
-// the part of the select workspace that does not depend on rocPRIM's answer
-static size_t topk_fixed_bytes(int64_t n, int64_t G, int64_t max_n) {
-  if (max_n <= tuned_topk_wg_limit()) return 256;
-  const size_t nn = (size_t)(n > 0 ? n : 1), gg = (size_t)(G > 0 ? G : 1);
-  return 2 * align_up(nn * 8, 256) + 2 * align_up(gg * 8, 256);
-}
+// mp_topk_select_f32's workspace on the sorted path: the composites, their sorted
+// copy and the segment bounds, then the sort's temp.  The on-chip paths use no
+// workspace; the caller still passes kTopkOnChipWs bytes.
+constexpr size_t kTopkOnChipWs = 256;
+struct TopkSortWs : Carver {
+  int64_t n, G;
+  uint64_t* keys = take<uint64_t>(n);
+  uint64_t* keys_out = take<uint64_t>(n);
+  int64_t* seg_begin = take<int64_t>(G);
+  int64_t* seg_end = take<int64_t>(G);
+};
+
+// mp_pool_score_bwd_f32's workspace: du and z of every row, the per-chunk partials
+struct ScoreBwdWs : Carver {
+  int64_t n, F;
+  float* du = take<float>(n);
+  float* z = take<float>(n);
+  float* part = take<float>(mp_pool_score_bwd_parts(n) * ((F > 0 ? F : 1) + 1));
+};
 
 // ---- gate ------------------------------------------------------------------
 
@@ -488,12 +491,12 @@ __global__ void k_pool_edge_emit(const int64_t* __restrict__ row, const int64_t*
   out_col[k] = inv[col[p]];
 }
 
-static hipError_t pool_select_bytes(int64_t n, size_t* bytes) {
-  *bytes = 0;
-  rocprim::counting_iterator<int64_t> it(0);
-  return rocprim::select((void*)nullptr, *bytes, it, (const uint8_t*)nullptr, (int64_t*)nullptr,
-                         (unsigned long long*)nullptr, (size_t)(n > 0 ? n : 1), (hipStream_t)0, false);
-}
+// mp_pool_filter_adj's workspace: keep flag per edge, then the select's temp
+// (mp_pool_compact's is the select's temp alone: a bare Carver)
+struct FilterAdjWs : Carver {
+  int64_t n_edges;
+  uint8_t* keep = take<uint8_t>(n_edges);
+};
 
 }  // namespace mp
 
@@ -550,7 +553,7 @@ int mp_pool_score_f32(const float* attn, int64_t ld, int64_t n, int32_t F, const
   MP_CHECK_ARG(n == 0 || score, "mp_pool_score_f32: score is NULL");
   MP_CHECK_EXTENT("mp_pool_score_f32", "score", score_bytes, (size_t)n * sizeof(float));
   if (n == 0) return MP_OK;
-  const int gl = pool_group_lanes(F);
+  const int gl = group_lanes(F);
   k_pool_score<<<pool_row_blocks(n, gl), kPoolBlock, 0, as_stream(stream)>>>(attn, ld, n, F, w, flags, gl, score);
   MP_CHECK_LAUNCH();
   return MP_OK;
@@ -562,8 +565,7 @@ int32_t mp_pool_score_bwd_parts(int64_t n) {
 }
 
 size_t mp_pool_score_bwd_workspace(int64_t n, int32_t F) {
-  const size_t nn = (size_t)(n > 0 ? n : 1), ff = (size_t)(F > 0 ? F : 1);
-  return 2 * align_up(nn * 4, 256) + align_up((size_t)mp_pool_score_bwd_parts(n) * (ff + 1) * 4, 256);
+  return ScoreBwdWs{nullptr, n, F}.off;
 }
 
 int mp_pool_score_bwd_f32(const float* attn, int64_t ld, int64_t n, int32_t F, const float* w, int32_t flags,
@@ -584,28 +586,23 @@ int mp_pool_score_bwd_f32(const float* attn, int64_t ld, int64_t n, int32_t F, c
   MP_CHECK_ARG(n == 0 || score || !(flags & MP_POOL_SCORE_TANH), "mp_pool_score_bwd_f32: score is NULL");
   MP_CHECK_ARG(ws, "mp_pool_score_bwd_f32: ws is NULL");
   MP_CHECK_EXTENT("mp_pool_score_bwd_f32", "g_w", g_w_bytes, (size_t)F * sizeof(float));
-  MP_CHECK_EXTENT("mp_pool_score_bwd_f32", "ws", ws_bytes, mp_pool_score_bwd_workspace(n, F));
+  const ScoreBwdWs l{ws, n, F};
+  MP_CHECK_EXTENT("mp_pool_score_bwd_f32", "ws", ws_bytes, l.off);
   hipStream_t s = as_stream(stream);
   if (n == 0) {
     MP_CHECK_HIP(hipMemsetAsync(g_w, 0, (size_t)F * sizeof(float), s));
     return MP_OK;
   }
-  char* p = (char*)ws;
-  float* du = (float*)p;
-  p += align_up((size_t)n * 4, 256);
-  float* z = (float*)p;
-  p += align_up((size_t)n * 4, 256);
-  float* part = (float*)p;
-  const int gl = pool_group_lanes(F);
+  const int gl = group_lanes(F);
   k_pool_score_bwd_rows<<<pool_row_blocks(n, gl), kPoolBlock, 0, s>>>(attn, ld, n, F, w, flags, gl, score, g_score,
-                                                                     g_attn, ldg, du, z);
+                                                                     g_attn, ldg, l.du, l.z);
   MP_CHECK_LAUNCH();
   const int parts = mp_pool_score_bwd_parts(n);
   const int64_t chunk = ceil_div(n, parts);
-  k_pool_score_bwd_parts<<<dim3((unsigned)parts, (unsigned)ceil_div(F + 1, 64)), kPoolBlock, 0, s>>>(attn, ld, n, F,
-                                                                                                    chunk, du, z, part);
+  k_pool_score_bwd_parts<<<dim3((unsigned)parts, (unsigned)ceil_div(F + 1, 64)), kPoolBlock, 0, s>>>(
+      attn, ld, n, F, chunk, l.du, l.z, l.part);
   MP_CHECK_LAUNCH();
-  k_pool_score_bwd_finish<<<1, kPoolBlock, 0, s>>>(part, parts, F, w, flags, g_w);
+  k_pool_score_bwd_finish<<<1, kPoolBlock, 0, s>>>(l.part, parts, F, w, flags, g_w);
   MP_CHECK_LAUNCH();
   return MP_OK;
 }
@@ -627,11 +624,10 @@ int mp_topk_counts(const int64_t* starts, int64_t n_graphs, float ratio, int64_t
 }
 
 size_t mp_topk_workspace(int64_t n, int64_t n_graphs, int64_t max_n) {
-  size_t fixed = topk_fixed_bytes(n, n_graphs, max_n);
-  if (max_n <= tuned_topk_wg_limit()) return fixed;
+  if (max_n <= tuned_topk_wg_limit()) return kTopkOnChipWs;
   size_t sort = 0;
   (void)topk_sort_bytes(n, n_graphs, &sort);
-  return fixed + align_up(sort, 256) + 256;
+  return TopkSortWs{nullptr, n, n_graphs}.total(sort);
 }
 
 int mp_topk_select_f32(const float* score, int64_t n, const int64_t* starts, int64_t n_graphs, int64_t max_n,
@@ -657,12 +653,13 @@ int mp_topk_select_f32(const float* score, int64_t n, const int64_t* starts, int
   MP_CHECK_EXTENT("mp_topk_select_f32", "out_starts", out_starts_bytes, (size_t)(n_graphs + 1) * sizeof(int64_t));
   const int64_t limit = tuned_topk_wg_limit();
   const bool sorted = max_n > limit;
-  MP_CHECK_EXTENT("mp_topk_select_f32", "ws", ws_bytes, topk_fixed_bytes(n, n_graphs, max_n));
+  const TopkSortWs w{ws, n, n_graphs};
+  MP_CHECK_EXTENT("mp_topk_select_f32", "ws", ws_bytes, sorted ? w.off : kTopkOnChipWs);
   size_t sort_bytes = 0;
   if (sorted) {
-    MP_CHECK_HIP(topk_sort_bytes(n, n_graphs, &sort_bytes));
-    MP_CHECK_EXTENT("mp_topk_select_f32", "ws", ws_bytes,
-                    topk_fixed_bytes(n, n_graphs, max_n) + align_up(sort_bytes, 256) + 256);
+    const hipError_t size_query = topk_sort_bytes(n, n_graphs, &sort_bytes);
+    MP_CHECK_EXTENT("mp_topk_select_f32", "ws", ws_bytes, w.total(sort_bytes));
+    MP_CHECK_HIP(size_query);
   }
   hipStream_t s = as_stream(stream);
   k_topk_plan<<<1, 1024, 0, s>>>(starts, n_graphs, ratio, max_n, out_starts, counts);
@@ -678,28 +675,20 @@ int mp_topk_select_f32(const float* score, int64_t n, const int64_t* starts, int
     MP_CHECK_LAUNCH();
   }
   if (sorted) {
-    char* p = (char*)ws;
-    uint64_t* keys = (uint64_t*)p;
-    p += align_up((size_t)n * 8, 256);
-    uint64_t* keys_out = (uint64_t*)p;
-    p += align_up((size_t)n * 8, 256);
-    int64_t* seg_begin = (int64_t*)p;
-    p += align_up((size_t)n_graphs * 8, 256);
-    int64_t* seg_end = (int64_t*)p;
-    p += align_up((size_t)n_graphs * 8, 256);
-    void* tmp = p;
-    k_topk_sort_keys<<<(unsigned)ceil_div(n, kPoolBlock), kPoolBlock, 0, s>>>(score, n, starts, n_graphs, cap, keys);
+    k_topk_sort_keys<<<(unsigned)ceil_div(n, kPoolBlock), kPoolBlock, 0, s>>>(score, n, starts, n_graphs, cap, w.keys);
     MP_CHECK_LAUNCH();
     if (n_graphs == 1) {
-      MP_CHECK_HIP(rocprim::radix_sort_keys_desc(tmp, sort_bytes, keys, keys_out, (size_t)n, 0u, 64u, s, false));
+      MP_CHECK_HIP(rocprim::radix_sort_keys_desc(w.rest(), sort_bytes, w.keys, w.keys_out, (size_t)n, 0u, 64u, s,
+                                                 false));
     } else {
-      k_topk_segments<<<(unsigned)ceil_div(n_graphs, kPoolBlock), kPoolBlock, 0, s>>>(starts, n_graphs, cap, seg_begin,
-                                                                                      seg_end);
+      k_topk_segments<<<(unsigned)ceil_div(n_graphs, kPoolBlock), kPoolBlock, 0, s>>>(starts, n_graphs, cap,
+                                                                                      w.seg_begin, w.seg_end);
       MP_CHECK_LAUNCH();
-      MP_CHECK_HIP(rocprim::segmented_radix_sort_keys_desc(tmp, sort_bytes, keys, keys_out, (size_t)n,
-                                                           (unsigned)n_graphs, seg_begin, seg_end, 0u, 64u, s, false));
+      MP_CHECK_HIP(rocprim::segmented_radix_sort_keys_desc(w.rest(), sort_bytes, w.keys, w.keys_out, (size_t)n,
+                                                           (unsigned)n_graphs, w.seg_begin, w.seg_end, 0u, 64u, s,
+                                                           false));
     }
-    k_topk_sort_emit<<<(unsigned)ceil_div(n, kPoolBlock), kPoolBlock, 0, s>>>(keys_out, n, starts, n_graphs, cap,
+    k_topk_sort_emit<<<(unsigned)ceil_div(n, kPoolBlock), kPoolBlock, 0, s>>>(w.keys_out, n, starts, n_graphs, cap,
                                                                               out_starts, perm, inv);
     MP_CHECK_LAUNCH();
   }
@@ -726,11 +715,11 @@ int mp_pool_gate_f32(const float* x, int64_t ldx, const float* score, const int6
   hipStream_t s = as_stream(stream);
   const int use_mult = multiplier != 1.f;
   if (pool_vec4_ok(F, x, ldx, x_out, ldo)) {
-    const int gl = pool_group_lanes(F / 4);
+    const int gl = group_lanes(F / 4);
     k_pool_gate<4><<<pool_row_blocks(k, gl), kPoolBlock, 0, s>>>(x, ldx, score, batch, perm, k, n, F / 4, multiplier,
                                                                 use_mult, gl, x_out, ldo, batch_out, score_out);
   } else {
-    const int gl = pool_group_lanes(F);
+    const int gl = group_lanes(F);
     k_pool_gate<1><<<pool_row_blocks(k, gl), kPoolBlock, 0, s>>>(x, ldx, score, batch, perm, k, n, F, multiplier,
                                                                 use_mult, gl, x_out, ldo, batch_out, score_out);
   }
@@ -761,11 +750,11 @@ int mp_pool_gate_bwd_f32(const float* g_y, int64_t ldgy, const float* g_t, const
   hipStream_t s = as_stream(stream);
   const int use_mult = multiplier != 1.f;
   if (pool_vec4_ok(F, x, ldx, g_x, ldgx) && ldgy % 4 == 0 && (uintptr_t)g_y % 16 == 0) {
-    const int gl = pool_group_lanes(F / 4);
+    const int gl = group_lanes(F / 4);
     k_pool_gate_bwd<4><<<pool_row_blocks(n, gl), kPoolBlock, 0, s>>>(g_y, ldgy, g_t, x, ldx, score, inv, k, n, F / 4,
                                                                     multiplier, use_mult, gl, g_x, ldgx, g_s);
   } else {
-    const int gl = pool_group_lanes(F);
+    const int gl = group_lanes(F);
     k_pool_gate_bwd<1><<<pool_row_blocks(n, gl), kPoolBlock, 0, s>>>(g_y, ldgy, g_t, x, ldx, score, inv, k, n, F,
                                                                     multiplier, use_mult, gl, g_x, ldgx, g_s);
   }
@@ -792,9 +781,9 @@ int mp_pool_inverse(const int64_t* perm, int64_t k, const int64_t* k_dev, int64_
 }
 
 size_t mp_pool_compact_workspace(int64_t n) {
-  size_t b = 0;
-  (void)pool_select_bytes(n, &b);
-  return align_up(b, 256) + 256;
+  size_t sel = 0;
+  (void)select_positions_bytes(n, &sel);
+  return Carver(nullptr).total(sel);
 }
 
 int mp_pool_compact(const uint8_t* keep, int64_t n, int64_t* out_pos, size_t out_pos_bytes, int64_t* count_dev,
@@ -807,25 +796,27 @@ int mp_pool_compact(const uint8_t* keep, int64_t n, int64_t* out_pos, size_t out
   MP_CHECK_ARG(n == 0 || out_pos, "mp_pool_compact: out_pos is NULL");
   MP_CHECK_ARG(ws, "mp_pool_compact: ws is NULL");
   MP_CHECK_EXTENT("mp_pool_compact", "out_pos", out_pos_bytes, (size_t)n * sizeof(int64_t));
-  MP_CHECK_EXTENT("mp_pool_compact", "ws", ws_bytes, 256);
+  const Carver w(ws);
+  MP_CHECK_EXTENT("mp_pool_compact", "ws", ws_bytes, w.total(0));
   hipStream_t s = as_stream(stream);
   if (n == 0) {
     MP_CHECK_HIP(hipMemsetAsync(count_dev, 0, sizeof(int64_t), s));
     return MP_OK;
   }
   size_t sel = 0;
-  MP_CHECK_HIP(pool_select_bytes(n, &sel));
-  MP_CHECK_EXTENT("mp_pool_compact", "ws", ws_bytes, align_up(sel, 256) + 256);
+  const hipError_t size_query = select_positions_bytes(n, &sel);
+  MP_CHECK_EXTENT("mp_pool_compact", "ws", ws_bytes, w.total(sel));
+  MP_CHECK_HIP(size_query);
   rocprim::counting_iterator<int64_t> it(0);
-  MP_CHECK_HIP(rocprim::select(ws, sel, it, keep, out_pos, reinterpret_cast<unsigned long long*>(count_dev), (size_t)n,
-                               s, false));
+  MP_CHECK_HIP(rocprim::select(w.rest(), sel, it, keep, out_pos, reinterpret_cast<unsigned long long*>(count_dev),
+                               (size_t)n, s, false));
   return MP_OK;
 }
 
 size_t mp_pool_filter_workspace(int64_t n_edges) {
-  size_t b = 0;
-  (void)pool_select_bytes(n_edges, &b);
-  return align_up((size_t)(n_edges > 0 ? n_edges : 1), 256) + align_up(b, 256) + 256;
+  size_t sel = 0;
+  (void)select_positions_bytes(n_edges, &sel);
+  return FilterAdjWs{nullptr, n_edges}.total(sel);
 }
 
 int mp_pool_filter_adj(const int64_t* row, const int64_t* col, int64_t n_edges, const int64_t* inv, int64_t n_nodes,
@@ -844,21 +835,21 @@ int mp_pool_filter_adj(const int64_t* row, const int64_t* col, int64_t n_edges, 
   MP_CHECK_ARG(n_edges == 0 || out_pos, "mp_pool_filter_adj: out_pos is NULL");
   MP_CHECK_ARG(ws, "mp_pool_filter_adj: ws is NULL");
   MP_CHECK_EXTENT("mp_pool_filter_adj", "out_row / out_col / out_pos", out_bytes, (size_t)n_edges * sizeof(int64_t));
-  MP_CHECK_EXTENT("mp_pool_filter_adj", "ws", ws_bytes, align_up((size_t)(n_edges > 0 ? n_edges : 1), 256) + 256);
+  const FilterAdjWs w{ws, n_edges};
+  MP_CHECK_EXTENT("mp_pool_filter_adj", "ws", ws_bytes, w.total(0));
   hipStream_t s = as_stream(stream);
   MP_CHECK_HIP(hipMemsetAsync(counts + 1, 0, 2 * sizeof(int64_t), s));
   if (n_edges == 0) return MP_OK;
   size_t sel = 0;
-  MP_CHECK_HIP(pool_select_bytes(n_edges, &sel));
-  MP_CHECK_EXTENT("mp_pool_filter_adj", "ws", ws_bytes, align_up((size_t)n_edges, 256) + align_up(sel, 256) + 256);
-  uint8_t* keep = (uint8_t*)ws;
-  void* tmp = (char*)ws + align_up((size_t)n_edges, 256);
+  const hipError_t size_query = select_positions_bytes(n_edges, &sel);
+  MP_CHECK_EXTENT("mp_pool_filter_adj", "ws", ws_bytes, w.total(sel));
+  MP_CHECK_HIP(size_query);
   const unsigned blocks = (unsigned)ceil_div(n_edges, kPoolBlock);
-  k_pool_edge_flags<<<blocks, kPoolBlock, 0, s>>>(row, col, n_edges, inv, n_nodes, keep,
+  k_pool_edge_flags<<<blocks, kPoolBlock, 0, s>>>(row, col, n_edges, inv, n_nodes, w.keep,
                                                   reinterpret_cast<unsigned long long*>(counts));
   MP_CHECK_LAUNCH();
   rocprim::counting_iterator<int64_t> it(0);
-  MP_CHECK_HIP(rocprim::select(tmp, sel, it, keep, out_pos, reinterpret_cast<unsigned long long*>(counts + 1),
+  MP_CHECK_HIP(rocprim::select(w.rest(), sel, it, w.keep, out_pos, reinterpret_cast<unsigned long long*>(counts + 1),
                                (size_t)n_edges, s, false));
   k_pool_edge_emit<<<blocks, kPoolBlock, 0, s>>>(row, col, inv, out_pos, counts + 1, n_edges, out_row, out_col);
   MP_CHECK_LAUNCH();

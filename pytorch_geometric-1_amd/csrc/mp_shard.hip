@@ -12,10 +12,8 @@
 // Replaces the torch-op plan of mi355_mp.dist.ShardPlan (nonzero / unique /
 // searchsorted) for device edge lists.
 #include <rocprim/device/device_scan.hpp>
-#include <rocprim/device/device_select.hpp>
-#include <rocprim/iterator/counting_iterator.hpp>
 
-#include "mp_common.h"
+#include "mp_workspace.h"
 
 namespace mp {
 
@@ -74,20 +72,20 @@ __global__ void k_plan_counts(const int32_t* __restrict__ flag, const int32_t* _
   if (q < world) counts[2 + q] = before(cuts[q + 1]) - before(cuts[q]);
 }
 
-static size_t plan_select_bytes(int64_t n) {
-  size_t bytes = 0;
-  rocprim::counting_iterator<int64_t> it(0);
-  (void)rocprim::select((void*)nullptr, bytes, it, (const uint8_t*)nullptr, (int64_t*)nullptr,
-                        (unsigned long long*)nullptr, (size_t)(n > 0 ? n : 1), (hipStream_t)0, false);
-  return bytes;
+static hipError_t plan_scan_bytes(int64_t n, size_t* bytes) {
+  return rocprim::exclusive_scan((void*)nullptr, *bytes, (const int32_t*)nullptr, (int32_t*)nullptr, 0,
+                                 (size_t)(n > 0 ? n : 1), rocprim::plus<int32_t>(), (hipStream_t)0, false);
 }
 
-static size_t plan_scan_bytes(int64_t n) {
-  size_t bytes = 0;
-  (void)rocprim::exclusive_scan((void*)nullptr, bytes, (const int32_t*)nullptr, (int32_t*)nullptr, 0,
-                                (size_t)(n > 0 ? n : 1), rocprim::plus<int32_t>(), (hipStream_t)0, false);
-  return bytes;
-}
+// mp_shard_plan's workspace, then the temp the select and the scan share (the larger of the two)
+struct ShardPlanWs : Carver {
+  int64_t n_edges, n_nodes;
+  uint8_t* keep = take<uint8_t>(n_edges);
+  int32_t* flag = take<int32_t>(n_nodes);
+  int32_t* hidx = take<int32_t>(n_nodes);
+  unsigned long long* n_sel = take<unsigned long long>(1);
+  int32_t* bad = take<int32_t>(1);
+};
 
 }  // namespace mp
 
@@ -96,10 +94,10 @@ using namespace mp;
 extern "C" {
 
 size_t mp_shard_plan_workspace(int64_t n_edges, int64_t n_nodes) {
-  const size_t e = (size_t)(n_edges > 0 ? n_edges : 1);
-  const size_t n = (size_t)(n_nodes > 0 ? n_nodes : 1);
-  const size_t tmp = std::max(plan_select_bytes(n_edges), plan_scan_bytes(n_nodes));
-  return align_up(e, 256) + 2 * align_up(n * 4, 256) + 2 * align_up(8, 256) + align_up(tmp, 256) + 256;
+  size_t sel_bytes = 0, scan_bytes = 0;
+  (void)select_positions_bytes(n_edges, &sel_bytes);
+  (void)plan_scan_bytes(n_nodes, &scan_bytes);
+  return ShardPlanWs{nullptr, n_edges, n_nodes}.total(std::max(sel_bytes, scan_bytes));
 }
 
 int mp_shard_plan(const int64_t* key, const int64_t* other, int64_t n_edges, int64_t n_nodes, const int64_t* cuts,
@@ -114,44 +112,36 @@ int mp_shard_plan(const int64_t* key, const int64_t* other, int64_t n_edges, int
   MP_CHECK_ARG(n_edges == 0 || (key && other && edge_pos && local_key && local_other),
                "mp_shard_plan: null edge array");
   MP_CHECK_ARG(n_nodes == 0 || halo_nodes, "mp_shard_plan: null halo_nodes");
-  MP_CHECK_ARG(ws && ws_bytes >= mp_shard_plan_workspace(n_edges, n_nodes), "mp_shard_plan: workspace too small");
+  const ShardPlanWs w{ws, n_edges, n_nodes};
+  size_t sel_bytes = 0, scan_bytes = 0;
+  const hipError_t sel_query = select_positions_bytes(n_edges, &sel_bytes);
+  const hipError_t scan_query = plan_scan_bytes(n_nodes, &scan_bytes);
+  MP_CHECK_ARG(ws && ws_bytes >= w.total(std::max(sel_bytes, scan_bytes)), "mp_shard_plan: workspace too small");
+  MP_CHECK_HIP(sel_query);
+  MP_CHECK_HIP(scan_query);
   hipStream_t s = as_stream(stream);
-  char* p = (char*)ws;
-  uint8_t* keep = (uint8_t*)p;
-  p += align_up((size_t)(n_edges > 0 ? n_edges : 1), 256);
-  int32_t* flag = (int32_t*)p;
-  p += align_up((size_t)(n_nodes > 0 ? n_nodes : 1) * 4, 256);
-  int32_t* hidx = (int32_t*)p;
-  p += align_up((size_t)(n_nodes > 0 ? n_nodes : 1) * 4, 256);
-  unsigned long long* n_sel = (unsigned long long*)p;
-  p += align_up(8, 256);
-  int32_t* bad = (int32_t*)p;
-  p += align_up(8, 256);
-  void* tmp = p;
   const int B = 256;
-  MP_CHECK_HIP(hipMemsetAsync(n_sel, 0, 8, s));
-  MP_CHECK_HIP(hipMemsetAsync(bad, 0, 4, s));
-  if (n_nodes > 0) MP_CHECK_HIP(hipMemsetAsync(flag, 0, (size_t)n_nodes * 4, s));
+  MP_CHECK_HIP(hipMemsetAsync(w.n_sel, 0, 8, s));
+  MP_CHECK_HIP(hipMemsetAsync(w.bad, 0, 4, s));
+  if (n_nodes > 0) MP_CHECK_HIP(hipMemsetAsync(w.flag, 0, (size_t)n_nodes * 4, s));
   if (n_edges > 0) {
-    k_plan_flags<<<ceil_div(n_edges, B), B, 0, s>>>(key, other, n_edges, n_nodes, lo, hi, keep, flag, bad);
+    k_plan_flags<<<ceil_div(n_edges, B), B, 0, s>>>(key, other, n_edges, n_nodes, lo, hi, w.keep, w.flag, w.bad);
     MP_CHECK_LAUNCH();
-    size_t sel_bytes = plan_select_bytes(n_edges);
     rocprim::counting_iterator<int64_t> it(0);
-    MP_CHECK_HIP(rocprim::select(tmp, sel_bytes, it, keep, edge_pos, n_sel, (size_t)n_edges, s, false));
+    MP_CHECK_HIP(rocprim::select(w.rest(), sel_bytes, it, w.keep, edge_pos, w.n_sel, (size_t)n_edges, s, false));
   }
   if (n_nodes > 0) {
-    size_t scan_bytes = plan_scan_bytes(n_nodes);
-    MP_CHECK_HIP(rocprim::exclusive_scan(tmp, scan_bytes, flag, hidx, 0, (size_t)n_nodes, rocprim::plus<int32_t>(),
-                                         s, false));
-    k_plan_halo<<<ceil_div(n_nodes, B), B, 0, s>>>(flag, hidx, n_nodes, halo_nodes);
+    MP_CHECK_HIP(rocprim::exclusive_scan(w.rest(), scan_bytes, w.flag, w.hidx, 0, (size_t)n_nodes,
+                                         rocprim::plus<int32_t>(), s, false));
+    k_plan_halo<<<ceil_div(n_nodes, B), B, 0, s>>>(w.flag, w.hidx, n_nodes, halo_nodes);
     MP_CHECK_LAUNCH();
   }
   if (n_edges > 0) {
-    k_plan_local<<<ceil_div(n_edges, B), B, 0, s>>>(key, other, edge_pos, n_sel, n_nodes, lo, hi, hidx,
+    k_plan_local<<<ceil_div(n_edges, B), B, 0, s>>>(key, other, edge_pos, w.n_sel, n_nodes, lo, hi, w.hidx,
                                                     local_key, local_other);
     MP_CHECK_LAUNCH();
   }
-  k_plan_counts<<<1, 1024, 0, s>>>(flag, hidx, n_nodes, cuts, world, n_sel, bad, counts);
+  k_plan_counts<<<1, 1024, 0, s>>>(w.flag, w.hidx, n_nodes, cuts, world, w.n_sel, w.bad, counts);
   MP_CHECK_LAUNCH();
   return MP_OK;
 }

@@ -180,6 +180,46 @@ def test_every_partial_array_carries_its_extent(lib):
     assert rc == 1 and b"att_part" in lib.mp_last_error()
 
 
+def test_workspace_one_byte_short_is_rejected(lib):
+    """Every entry point that carves a caller-allocated workspace rejects one of
+    mp_*_workspace() - 1 bytes before any launch: the size function and the
+    entry point read one layout (csrc/mp_workspace.h), so an array added to one
+    cannot be forgotten in the other."""
+    D = 0x7F0000000000            # fake device pointer: never dereferenced, the check fails first
+    N, E, F = 1000, 3000, 33
+    nw = lib.mp_schedule_n_waves(N, E, 256)
+    cases = [
+        ("mp_csr_build", lib.mp_csr_build_workspace(E, N), lambda b: (D, D, E, N, N, D, D, D, D, D, b, None)),
+        ("mp_schedule_build", lib.mp_schedule_workspace(nw), lambda b: (D, N, E, 256, 24, D, D, D, D, D, b, None)),
+        ("mp_self_loops", lib.mp_self_loops_workspace(E, N), lambda b: (D, D, E, N, 2, E - 5, D, D, D, D, b, None)),
+        ("mp_shard_plan", lib.mp_shard_plan_workspace(E, N),
+         lambda b: (D, D, E, N, D, 2, 0, 0, N // 2, D, D, D, D, D, D, b, None)),
+        ("mp_pool_score_bwd_f32", lib.mp_pool_score_bwd_workspace(N, F),
+         lambda b: (D, F, N, F, D, 1, D, D, D, F, D, F * 4, D, b, None)),
+        ("mp_topk_select_f32", lib.mp_topk_workspace(N, 7, 64),
+         lambda b: (D, N, D, 7, 64, 0.5, D, N * 8, D, 64, D, N * 8, D, D, b, None)),
+        ("mp_pool_compact", lib.mp_pool_compact_workspace(N), lambda b: (D, N, D, N * 8, D, D, b, None)),
+        ("mp_pool_filter_adj", lib.mp_pool_filter_workspace(E), lambda b: (D, D, E, D, N, D, D, D, E * 8, D, D, b, None)),
+        ("mp_cluster_build", lib.mp_cluster_build_workspace(N),
+         lambda b: (D, N, D, N * 8, D, (N + 1) * 4, D, N * 4, D, N * 8, D, D, b, None)),
+        ("mp_cluster_edges", lib.mp_cluster_edges_workspace(E, N),
+         lambda b: (D, D, E, D, N, D, D, D, D, E * 8, D, (E + 1) * 4, D, E * 4, D, b, None)),
+    ]
+    assert cases[5][1] == 256                                      # the on-chip select paths
+    for graphs in (1, 3):                                          # the sorted path: one graph, several
+        need = lib.mp_topk_workspace(10000, graphs, 10000)
+        assert need > 2 * 10000 * 8
+        cases.append(("mp_topk_select_f32", need,
+                      lambda b, g=graphs: (D, 10000, D, g, 10000, 0.5, D, 80000, D, (g + 1) * 8, D, 80000, D, D, b, None)))
+    assert len({c[0] for c in cases}) == 10 and len(cases) == 12
+    for name, need, args in cases:
+        assert need >= 256, name
+        rc = getattr(lib, name)(*args(need - 1))
+        err = lib.mp_last_error().decode()
+        assert rc == 1 and name in err, (name, need, rc, err)
+        assert "workspace too small" in err or "ws holds %d bytes, the call needs %d" % (need - 1, need) in err, err
+
+
 def test_extent_arguments_in_the_header():
     """Every ABI-6 extent is declared next to its array in include/mi355_mp.h and
     in the ctypes signatures (size_t after the pointer)."""
