@@ -407,7 +407,34 @@ __global__ __launch_bounds__(kPoolBlock) void k_pool_gate(const float* __restric
   }
 }
 
-template <int VEC>
+// A fragment of VEC floats by one vector access (ALIGNED: 16-byte aligned rows) or by VEC scalar ones
+template <int VEC, bool ALIGNED>
+__device__ __forceinline__ Frag<VEC> pool_load(const float* p) {
+  if constexpr (ALIGNED) {
+    return load_frag<VEC>(p);
+  } else {
+    Frag<VEC> r;
+#pragma unroll
+    for (int q = 0; q < VEC; ++q) r.v[q] = p[q];
+    return r;
+  }
+}
+
+template <int VEC, bool ALIGNED>
+__device__ __forceinline__ void pool_store(float* p, const Frag<VEC>& f) {
+  if constexpr (ALIGNED) {
+    store_frag<VEC>(p, f);
+  } else {
+#pragma unroll
+    for (int q = 0; q < VEC; ++q) p[q] = f.v[q];
+  }
+}
+
+// g_s[i] = mult * <g_y[r, :], x[i, :]> is a sum: its order is fixed by VEC (a lane adds its VEC
+// consecutive features, then the lane group is added), so VEC follows F alone (4 when F % 4 == 0)
+// and rows that are not 16-byte aligned (a column slice of a wider tensor) keep VEC and only
+// change how a fragment is moved: the gradient does not depend on where x lies in memory
+template <int VEC, bool ALIGNED>
 __global__ __launch_bounds__(kPoolBlock) void k_pool_gate_bwd(const float* __restrict__ g_y, int64_t ldgy,
                                                               const float* __restrict__ g_t,
                                                               const float* __restrict__ x, int64_t ldx,
@@ -428,8 +455,8 @@ __global__ __launch_bounds__(kPoolBlock) void k_pool_gate_bwd(const float* __res
   for (int e = sub; e < FE; e += gl) {
     Frag<VEC> o;
     if (kept) {
-      const Frag<VEC> gy = load_frag<VEC>(g_y + r * ldgy + (int64_t)e * VEC);
-      const Frag<VEC> xv = load_frag<VEC>(x + i * ldx + (int64_t)e * VEC);
+      const Frag<VEC> gy = pool_load<VEC, ALIGNED>(g_y + r * ldgy + (int64_t)e * VEC);
+      const Frag<VEC> xv = pool_load<VEC, ALIGNED>(x + i * ldx + (int64_t)e * VEC);
 #pragma unroll
       for (int q = 0; q < VEC; ++q) {
         dot += gy.v[q] * xv.v[q];
@@ -439,7 +466,7 @@ __global__ __launch_bounds__(kPoolBlock) void k_pool_gate_bwd(const float* __res
 #pragma unroll
       for (int q = 0; q < VEC; ++q) o.v[q] = 0.f;
     }
-    if (valid) store_frag<VEC>(g_x + i * ldgx + (int64_t)e * VEC, o);
+    if (valid) pool_store<VEC, ALIGNED>(g_x + i * ldgx + (int64_t)e * VEC, o);
   }
   dot = group_sum(dot, gl);
   if (valid && sub == 0) {
@@ -749,14 +776,19 @@ int mp_pool_gate_bwd_f32(const float* g_y, int64_t ldgy, const float* g_t, const
   MP_CHECK_EXTENT("mp_pool_gate_bwd_f32", "g_s", g_s_bytes, (size_t)n * sizeof(float));
   hipStream_t s = as_stream(stream);
   const int use_mult = multiplier != 1.f;
-  if (pool_vec4_ok(F, x, ldx, g_x, ldgx) && ldgy % 4 == 0 && (uintptr_t)g_y % 16 == 0) {
+  if (F % 4 == 0) {
     const int gl = group_lanes(F / 4);
-    k_pool_gate_bwd<4><<<pool_row_blocks(n, gl), kPoolBlock, 0, s>>>(g_y, ldgy, g_t, x, ldx, score, inv, k, n, F / 4,
-                                                                    multiplier, use_mult, gl, g_x, ldgx, g_s);
+    if (pool_vec4_ok(F, x, ldx, g_x, ldgx) && ldgy % 4 == 0 && (uintptr_t)g_y % 16 == 0) {
+      k_pool_gate_bwd<4, true><<<pool_row_blocks(n, gl), kPoolBlock, 0, s>>>(
+          g_y, ldgy, g_t, x, ldx, score, inv, k, n, F / 4, multiplier, use_mult, gl, g_x, ldgx, g_s);
+    } else {
+      k_pool_gate_bwd<4, false><<<pool_row_blocks(n, gl), kPoolBlock, 0, s>>>(
+          g_y, ldgy, g_t, x, ldx, score, inv, k, n, F / 4, multiplier, use_mult, gl, g_x, ldgx, g_s);
+    }
   } else {
     const int gl = group_lanes(F);
-    k_pool_gate_bwd<1><<<pool_row_blocks(n, gl), kPoolBlock, 0, s>>>(g_y, ldgy, g_t, x, ldx, score, inv, k, n, F,
-                                                                    multiplier, use_mult, gl, g_x, ldgx, g_s);
+    k_pool_gate_bwd<1, true><<<pool_row_blocks(n, gl), kPoolBlock, 0, s>>>(g_y, ldgy, g_t, x, ldx, score, inv, k, n, F,
+                                                                          multiplier, use_mult, gl, g_x, ldgx, g_s);
   }
   MP_CHECK_LAUNCH();
   return MP_OK;

@@ -1819,7 +1819,10 @@ class _GatherByPos(torch.autograd.Function):
 
 def _gather_rows_bytes(attr, pos):
     """rows of any dtype whose elements are 2, 4 or 8 bytes wide (mp_gather_rows_any)."""
-    flat = attr.reshape(attr.shape[0], -1)
+    width = 1
+    for d in attr.shape[1:]:
+        width *= int(d)
+    flat = attr.reshape(attr.shape[0], width)            # not -1: ambiguous for a tensor of no rows (E = 0)
     if flat.stride(1) != 1 or flat.stride(0) < max(flat.shape[1], 1):
         flat = flat.contiguous()
     if flat.element_size() not in (2, 4, 8):

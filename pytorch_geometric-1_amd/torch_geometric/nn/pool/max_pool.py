@@ -53,6 +53,9 @@ def _pool_x(cluster, x, batch, size, reduce):
     _lib.require_device(cluster, x, batch)
     x2 = x.view(-1, 1) if x.dim() == 1 else x
     if size is not None:
+        if x2.shape[0] == 0:
+            # upstream sizes the output by batch.max() + 1: undefined without a node
+            raise RuntimeError("max_pool_x / avg_pool_x with size: no nodes (batch.max() of an empty batch)")
         rows = ops.num_graphs(batch, x2.shape[0]) * int(size)
         return ops.segment_reduce(x2, cluster, rows, reduce, pyg_mask=reduce == "max")[0], None
     sel = ops.cluster_build(cluster)

@@ -38,6 +38,9 @@ def _layout(batch, n, device):
 
 def _select(score, ratio, batch, min_score, tol, layout):
     if min_score is None:
+        if layout.n == 0:
+            # upstream takes num_nodes.max() of the per-graph node counts: no graph, nothing to reduce
+            raise RuntimeError("topk: no nodes (the largest graph of an empty batch is undefined)")
         return ops.topk_select(score, ratio, layout)
     return ops.select_min_score(score, float(min_score), batch, layout, tol)
 

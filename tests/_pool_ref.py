@@ -113,3 +113,35 @@ def layer(x, weight, perm, attn=None, multiplier=1, nonlinearity=torch.tanh, min
 def distinct_scores(m, generator):
     """m distinct float32 values in (-1, 1): tanh(randn) repeats values in fp32."""
     return ((torch.randperm(m, generator=generator).float() + 0.5) / m * 2 - 1)
+
+
+def layer_grad_scales(x, attn, weight, perm, gy, gt, multiplier):
+    """sum |terms| of the layer's gradients for the loss <x_out, gy> + <score[perm], gt>:
+    (gate_abs [n, F], attn_abs [n, Fa], w_abs [Fa]), the same computation on absolute
+    values.  x [n, F], attn [n, Fa] (x itself when the layer scores x) and weight are
+    float64; with r = inv[n], m = multiplier, z_abs = sum_f |attn_f w_f| and
+    s_abs = tanh(z_abs / ||w||) (the score of the absolute inputs):
+      g_s[n]    : gs_abs = m * sum_f |g_y[r, f] x[n, f]| + |g_t[r]|     (0 when dropped)
+      du_n      : du_abs = gs_abs * (1 + s_abs^2)     (tanh' is evaluated as 1 - s^2: terms 1 and s^2)
+      gate g_x  : m * s_abs * |g_y[r, :]|
+      g_attn    : du_abs / ||w|| * |w|
+      g_w       : sum_n du_abs |attn_n| / ||w|| + (sum_n du_abs z_abs) |w| / ||w||^3
+    (x's gradient is the sum of the gate and attn terms when attn is x.)"""
+    with torch.no_grad():
+        n, F = x.shape
+        m = float(multiplier)
+        att = attn.detach()
+        w = weight.detach().view(-1)
+        nrm = w.norm()
+        gy_n = torch.zeros(n, F, dtype=torch.float64)
+        gy_n[perm] = gy.double().abs()
+        gt_n = torch.zeros(n, dtype=torch.float64)
+        gt_n[perm] = gt.double().abs()
+        z_abs = (att * w).abs().sum(-1)
+        s_abs = torch.tanh(z_abs / nrm)
+        gs_abs = m * (gy_n * x.detach().abs()).sum(-1) + gt_n
+        du_abs = gs_abs * (1 + s_abs ** 2)
+        gate_abs = m * s_abs.view(-1, 1) * gy_n
+        attn_abs = du_abs.view(-1, 1) / nrm * w.abs().view(1, -1)
+        w_abs = (du_abs.view(-1, 1) * att.abs()).sum(0) / nrm + (du_abs * z_abs).sum() * w.abs() / nrm ** 3
+    return gate_abs, attn_abs, w_abs

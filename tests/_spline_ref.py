@@ -111,3 +111,32 @@ def spline_conv(x, edge_index, pseudo, weight, root, bias, kernel_size, is_open_
     if bias is not None:
         out = out + conv(bias)
     return out
+
+
+BOUND = 1e-5
+
+
+def assert_bound(got, ref, scale, what):
+    """|got - ref| <= 1e-5 * scale elementwise (scale = sum |terms|); prints the largest ratio."""
+    err = (got.detach().cpu().double() - ref.detach()).abs()
+    if not err.numel():
+        return
+    lim = BOUND * scale.detach()
+    worst = float((err - lim).max())
+    ratio = float((err / scale.detach().clamp(min=1e-300)).max())
+    print("%s: max |err| / sum|terms| = %.3g" % (what, ratio))
+    assert worst <= 0.0, "%s: |err| exceeds 1e-5 * sum|terms| by %.3g (max ratio %.3g)" % (what, worst, ratio)
+
+
+def abs_grad_scale(weight, root, bias, x, ei, u, ks, op, M, aggr, gout, flow="source_to_target"):
+    """sum |terms| of every gradient, {"x", "weight", "root", "bias"} (root / bias
+    when given): the float64 autograd of the restatement on absolute inputs with
+    |grad_out| (all terms >= 0, so the gradient of the absolute computation is
+    the sum of the terms' magnitudes)."""
+    leaves = {"x": x, "weight": weight, "root": root, "bias": bias}
+    leaves = {k: v.detach().cpu().abs().double().clone().requires_grad_(True) for k, v in leaves.items()
+              if v is not None}
+    out = spline_conv(leaves["x"], ei, u, leaves["weight"], leaves.get("root"), leaves.get("bias"), ks, op, M, aggr,
+                      flow)
+    (out * gout.double().abs()).sum().backward()
+    return {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}

@@ -20,6 +20,7 @@ import torch
 from hypothesis import HealthCheck, example, given, settings, strategies as st
 
 from oracle import pyg_ref as P
+from tests._fuzz_cases import graph as _graph
 
 pytestmark = pytest.mark.gpu
 
@@ -27,23 +28,6 @@ DEV = "cuda"
 _N_EX = int(os.environ.get("MP_FUZZ_LAYER_EXAMPLES", "60"))
 _SETTINGS = dict(max_examples=_N_EX, deadline=None, derandomize=True, database=None,
                  suppress_health_check=[HealthCheck.too_slow, HealthCheck.function_scoped_fixture])
-
-
-def _graph(N, deg, loops, seed, n_src=None):
-    """Random edge list with duplicates; `loops` of its edges made self loops
-    (some nodes get several).  n_src: bipartite source count (no loops)."""
-    g = torch.Generator().manual_seed(seed)
-    E = int(N * deg)
-    ns = N if n_src is None else n_src
-    ei = torch.stack([torch.randint(ns, (E,), generator=g), torch.randint(N, (E,), generator=g)])
-    if E and N > 1 and n_src is None:
-        hub = torch.randint(N, (1,), generator=g)
-        ei[1, : E // 4] = hub                       # one hub destination
-    if loops and E and n_src is None:
-        k = max(1, int(E * loops))
-        pos = torch.randint(E, (k,), generator=g)
-        ei[0, pos] = ei[1, pos]
-    return ei, g
 
 
 def _bound(got, want, terms, rel):
@@ -736,6 +720,73 @@ def test_float64_layers_gradcheck(layer):
             float((out.detach().cpu() - ref).abs().max())
 
 
+def _empty_graph_through_the_pooling_layers(N, ei):
+    """SplineConv, TopKPooling / filter_adj and cluster pooling on N nodes and no
+    edge (DESIGN 4.9 - 4.11 list the cases).  Where upstream raises on an input
+    without a node -- topk takes the largest graph of an empty batch,
+    voxel_grid and the sized max_pool_x take batch.max() -- the engine raises an
+    exception of the same kind from Python and enqueues nothing that could fail."""
+    from torch_geometric.data import Batch
+    from torch_geometric.nn import (SplineConv, TopKPooling, avg_pool, max_pool, max_pool_x, voxel_grid)
+    from torch_geometric.nn.pool import filter_adj, topk
+    x = torch.randn(N, 4, device=DEV, requires_grad=True)
+    conv = SplineConv(4, 3, dim=2, kernel_size=3).to(DEV)
+    out = conv(x, ei, torch.empty(0, 2, device=DEV))
+    assert tuple(out.shape) == (N, 3)
+    out.sum().backward()
+    assert x.grad is not None and x.grad.shape == x.shape
+    if N:   # no edge: the root transform and the bias alone
+        assert torch.allclose(out, torch.addmm(conv.bias, x, conv.root), rtol=1e-5, atol=1e-6)
+    pool = TopKPooling(4).to(DEV)
+    zeros = torch.zeros(N, dtype=torch.long, device=DEV)            # empty for N = 0, one graph for N = 5
+    for batch in (None, zeros):
+        x = torch.randn(N, 4, device=DEV, requires_grad=True)
+        if N == 0:
+            with pytest.raises(RuntimeError):
+                pool(x, ei, None, batch)
+            with pytest.raises(RuntimeError):
+                topk(x[:, 0], 0.5, zeros)
+            continue
+        xo, eo, ao, bo, perm, so = pool(x, ei, None, batch)
+        assert tuple(xo.shape) == (3, 4) and tuple(eo.shape) == (2, 0) and ao is None       # ceil(0.5 * 5) = 3
+        assert tuple(bo.shape) == tuple(perm.shape) == tuple(so.shape) == (3,) and eo.dtype == torch.long
+        (xo.sum() + so.sum()).backward()
+        assert x.grad is not None and x.grad.shape == x.shape and pool.weight.grad is not None
+        xo, eo, ao, _, _, _ = pool(x, ei, torch.empty(0, 2, device=DEV), batch)
+        assert tuple(eo.shape) == (2, 0) and tuple(ao.shape) == (0, 2)
+    perm = torch.arange(N // 2, device=DEV)
+    eo, ao = filter_adj(ei, torch.empty(0, device=DEV), perm, num_nodes=N)
+    assert tuple(eo.shape) == (2, 0) and tuple(ao.shape) == (0,)
+    # cluster pooling: N = 0 gives the empty graph (upstream's unique / scatter of nothing)
+    pos = torch.rand(N, 2, device=DEV) * 28
+    cluster = torch.arange(N, device=DEV) // 2
+    for fn in (max_pool, avg_pool):
+        x = torch.randn(N, 4, device=DEV, requires_grad=True)
+        d = fn(cluster, Batch(batch=zeros, x=x, pos=pos, edge_index=ei))
+        M = (N + 1) // 2
+        assert tuple(d.x.shape) == (M, 4) and tuple(d.pos.shape) == (M, 2) and tuple(d.batch.shape) == (M,)
+        assert tuple(d.edge_index.shape) == (2, 0) and d.edge_attr is None
+        d.x.sum().backward()
+        assert x.grad is not None and x.grad.shape == x.shape
+    x = torch.randn(N, 4, device=DEV, requires_grad=True)
+    xo, bo = max_pool_x(cluster, x, zeros)
+    assert tuple(xo.shape) == ((N + 1) // 2, 4) and tuple(bo.shape) == ((N + 1) // 2,)
+    xo.sum().backward()
+    assert x.grad is not None and x.grad.shape == x.shape
+    if N == 0:
+        with pytest.raises(RuntimeError):
+            max_pool_x(cluster, x, zeros, size=2)
+        with pytest.raises(RuntimeError):
+            voxel_grid(pos, zeros, 5, 0, 28)                       # batch.max() of nothing
+        with pytest.raises((RuntimeError, IndexError)):
+            voxel_grid(pos, zeros, 5)                               # pos.min() of nothing
+    else:
+        xo, bo = max_pool_x(cluster, x, zeros, size=3)
+        assert tuple(xo.shape) == (3, 4) and bo is None
+        assert tuple(voxel_grid(pos, zeros, 5, 0, 28).shape) == (N,)
+        assert tuple(voxel_grid(pos, zeros, 5).shape) == (N,)
+
+
 def test_empty_graphs_through_every_layer():
     """Zero nodes and zero edges (an empty mini-batch shard, a graph whose edges
     were all filtered): every layer returns [0, F_out] / [N, F_out] as upstream,
@@ -763,6 +814,7 @@ def test_empty_graphs_through_every_layer():
         e_w = torch.empty(0, device=DEV)
         ei2, w2 = add_remaining_self_loops(ei, e_w, 1, N)
         assert ei2.shape == (2, N) and w2.shape == (N,)
+        _empty_graph_through_the_pooling_layers(N, ei)
     src = torch.empty(0, 3, device=DEV)
     idx = torch.empty(0, dtype=torch.long, device=DEV)
     for name in ("add", "mean", "max", "min"):

@@ -319,22 +319,7 @@ def test_gradients_against_float64(own_attn, F, multiplier):
     rxo, rso, s = R.layer(x64, w64, p, attn=a64, multiplier=multiplier)
     ((rxo * gy.double()).sum() + (rso * gt.double()).sum()).backward()
 
-    with torch.no_grad():
-        m = float(multiplier)
-        att = (a64 if own_attn else x64).detach()
-        w = w64.detach().view(-1)
-        nrm = w.norm()
-        gy_n = torch.zeros(n, F, dtype=torch.float64)
-        gy_n[p] = gy.double().abs()
-        gt_n = torch.zeros(n, dtype=torch.float64)
-        gt_n[p] = gt.double().abs()
-        z_abs = (att * w).abs().sum(-1)
-        s_abs = torch.tanh(z_abs / nrm)
-        gs_abs = m * (gy_n * x64.detach().abs()).sum(-1) + gt_n
-        du_abs = gs_abs * (1 + s_abs ** 2)
-        gate_abs = m * s_abs.view(-1, 1) * gy_n
-        attn_abs = du_abs.view(-1, 1) / nrm * w.abs().view(1, -1)
-        w_abs = (du_abs.view(-1, 1) * att.abs()).sum(0) / nrm + (du_abs * z_abs).sum() * w.abs() / nrm ** 3
+    gate_abs, attn_abs, w_abs = R.layer_grad_scales(x64, a64 if own_attn else x64, w64, p, gy, gt, multiplier)
     if own_attn:
         _assert_bound(xd.grad, x64.grad, gate_abs, "grad x")
         _assert_bound(ad.grad, a64.grad, attn_abs, "grad attn")

@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from tests import _spline_ref as R
+from tests._fuzz_cases import pseudo as _pseudo
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,18 +39,6 @@ def _graph_edges():
     return ei[:, torch.randperm(ei.shape[1], generator=g)].contiguous()
 
 
-def _pseudo(E, D, ks, seed):
-    """Random coordinates in [0, 1] with exact 0, 1 and grid points k / ks."""
-    g = torch.Generator().manual_seed(seed)
-    u = torch.rand(E, D, generator=g)
-    u[0::17] = 0.0
-    u[1::17] = 1.0
-    for d in range(D):
-        k = torch.randint(0, ks[d] + 1, (len(u[2::17]),), generator=g)
-        u[2::17, d] = k.float() / ks[d]
-    return u
-
-
 @pytest.fixture(scope="module")
 def edges():
     ei = _graph_edges()
@@ -64,13 +53,7 @@ def graph(edges):
     return Graph(ei, N, N)
 
 
-def _assert_bound(got, ref, scale, what):
-    err = (got.detach().cpu().double() - ref.detach()).abs()
-    lim = BOUND * scale.detach()
-    worst = float((err - lim).max())
-    ratio = float((err / scale.detach().clamp(min=1e-300)).max())
-    print("%s: max |err| / sum|terms| = %.3g" % (what, ratio))
-    assert worst <= 0.0, "%s: |err| exceeds 1e-5 * sum|terms| by %.3g (max ratio %.3g)" % (what, worst, ratio)
+_assert_bound = R.assert_bound
 
 
 # 1. basis -------------------------------------------------------------------
@@ -253,13 +236,7 @@ def _abs_grad_scale(name, conv, x, ei, u, ks, op, M, aggr, gout):
     """sum |terms| of one gradient: the float64 autograd of the restatement on
     absolute inputs with |grad_out| (all terms >= 0, so the gradient of the
     absolute computation is the sum of the terms' magnitudes)."""
-    leaves = {"x": x.detach().abs().double().clone().requires_grad_(True),
-              "weight": conv.weight.detach().cpu().abs().double().clone().requires_grad_(True),
-              "root": conv.root.detach().cpu().abs().double().clone().requires_grad_(True),
-              "bias": conv.bias.detach().cpu().abs().double().clone().requires_grad_(True)}
-    out = R.spline_conv(leaves["x"], ei, u, leaves["weight"], leaves["root"], leaves["bias"], ks, op, M, aggr)
-    (out * gout.double().abs()).sum().backward()
-    return leaves[name].grad
+    return R.abs_grad_scale(conv.weight, conv.root, conv.bias, x, ei, u, ks, op, M, aggr, gout)[name]
 
 
 # 5. bit-exact ---------------------------------------------------------------
