@@ -7,6 +7,7 @@ Only plain pointers, sizes and the HIP stream handle cross the boundary.
 """
 import ctypes
 import os
+import types
 
 import torch
 
@@ -191,6 +192,16 @@ SIGNATURES = {
     "mp_cluster_edge_attr_bwd_f32": (ctypes.c_int, [c_p, i64, c_p, i64, i32, i64, c_p, i64, sz, c_p]),
 }
 
+# Of the symbols declared `int` / `int32_t`, these answer a question (a version,
+# a count, a yes / no); every other one returns a status: MP_OK, or a code with
+# the reason in mp_last_error().  (ctypes.c_int32 is ctypes.c_int, so the types
+# cannot tell the two kinds apart.)
+VALUE_RETURNING = ("mp_abi_version", "mp_schedule_n_waves", "mp_gat_train_ok", "mp_gat_two_pass_ok",
+                   "mp_gat_wide_ok", "mp_gat_bwd_blocks", "mp_arg_mask_words", "mp_spline_ok", "mp_topk_path",
+                   "mp_pool_score_bwd_parts", "mp_cluster_max_blocks")
+STATUS_RETURNING = tuple(name for name, (res, _) in SIGNATURES.items()
+                         if res is ctypes.c_int and name not in VALUE_RETURNING)
+
 _lib = None
 
 
@@ -230,16 +241,38 @@ def load(path=None):
     # loaded into the process (an A/B variant) binds its template kernel stubs to the
     # first build's same-named definitions and silently runs the first build's code.
     lib = ctypes.CDLL(p, mode=ctypes.RTLD_LOCAL)
+
+    def raise_on_status(rc, func, args):
+        if rc != MP_OK:
+            check(rc, func.__name__, lib)   # the text comes from the library that refused
+        return rc
+
+    lib.raising = types.SimpleNamespace()   # the view native() returns
     for name, (res, args) in SIGNATURES.items():
         fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
+        fn.restype, fn.argtypes = res, args
+        if name in STATUS_RETURNING:
+            # item access makes a function object of its own, so the errcheck set on it
+            # leaves lib.<name> (attribute access, cached) returning the code
+            fn = lib[name]
+            fn.restype, fn.argtypes, fn.errcheck = res, args, raise_on_status
+        setattr(lib.raising, name, fn)
     if lib.mp_abi_version() != ABI_VERSION:
         raise NativeLibraryStale("mi355_mp: %s has C-ABI %d, these bindings need %d" % (p, lib.mp_abi_version(),
                                                                                        ABI_VERSION))
     if path is None:
         _lib = lib
     return lib
+
+
+def native(path=None):
+    """The library load(path) returns, as a view whose status-returning
+    functions (STATUS_RETURNING) raise RuntimeError "<symbol> failed (code
+    <rc>): <mp_last_error() text>" on a nonzero status instead of returning it;
+    size queries, *_ok, counts and strings are load()'s plain functions.  The
+    package calls the library through this view, so a call the library rejects
+    (before any launch) cannot go unnoticed."""
+    return load(path).raising
 
 
 def library_hash(path=None):
@@ -279,14 +312,14 @@ def kernel_name(csr_struct, w, x, ldx, F, reduce, bias, out, ldo, device=None):
     """Demangled name of the main kernel mp_aggregate_f32 dispatches for these
     arguments (mp_aggregate_kernel_name)."""
     buf = ctypes.create_string_buffer(1024)
-    check(load().mp_aggregate_kernel_name(csr_struct, w, x, ldx, F, MP_REDUCE[reduce], bias, out, ldo, buf, 1024,
-                                          stream_ptr(device)), "mp_aggregate_kernel_name")
+    native().mp_aggregate_kernel_name(csr_struct, w, x, ldx, F, MP_REDUCE[reduce], bias, out, ldo, buf, 1024,
+                                      stream_ptr(device))
     return buf.value.decode()
 
 
-def check(rc, what):
+def check(rc, what, lib=None):
     if rc != MP_OK:
-        msg = load().mp_last_error().decode(errors="replace")
+        msg = (lib or load()).mp_last_error().decode(errors="replace")
         raise RuntimeError("%s failed (code %d): %s" % (what, rc, msg))
 
 

@@ -173,7 +173,7 @@ def _plan_launch(key, other, num_nodes, cuts, cuts_d, rank, world):
     full-size outputs (edge_pos, local key, local other, halo_nodes) and the
     device count vector [n edges, n halo, per-owner halo counts...]."""
     from . import _lib
-    lib = _lib.load()
+    nat = _lib.native()
     dev = key.device
     key = key.to(torch.int64).contiguous()
     other = other.to(torch.int64).contiguous()
@@ -183,11 +183,10 @@ def _plan_launch(key, other, num_nodes, cuts, cuts_d, rank, world):
     lother = torch.empty_like(edge_pos)
     halo = torch.empty(num_nodes, dtype=torch.int64, device=dev)
     counts = torch.empty(2 + world, dtype=torch.int64, device=dev)
-    ws = torch.empty(lib.mp_shard_plan_workspace(E, num_nodes), dtype=torch.uint8, device=dev)
-    _lib.check(lib.mp_shard_plan(key.data_ptr(), other.data_ptr(), E, num_nodes, cuts_d.data_ptr(), world, rank,
-                                 cuts[rank], cuts[rank + 1], edge_pos.data_ptr(), lkey.data_ptr(),
-                                 lother.data_ptr(), halo.data_ptr(), counts.data_ptr(), ws.data_ptr(),
-                                 ws.numel(), _lib.stream_ptr(dev)), "mp_shard_plan")
+    ws = torch.empty(nat.mp_shard_plan_workspace(E, num_nodes), dtype=torch.uint8, device=dev)
+    nat.mp_shard_plan(key.data_ptr(), other.data_ptr(), E, num_nodes, cuts_d.data_ptr(), world, rank, cuts[rank],
+                      cuts[rank + 1], edge_pos.data_ptr(), lkey.data_ptr(), lother.data_ptr(), halo.data_ptr(),
+                      counts.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev))
     return edge_pos, lkey, lother, halo, counts
 
 

@@ -186,7 +186,7 @@ class GatHaloCover:
         hold zeros), for decompose().  drop = (seed, p): attention dropout
         (training form).  keep: return saved outside training too (alpha)."""
         from . import _lib
-        lib = _lib.load()
+        nat = _lib.native()
         g_loc, g_send, g_merge, _, g_push = self.graphs()
         train = train or drop is not None
         dev = xw_own.device
@@ -194,14 +194,13 @@ class GatHaloCover:
         n_own, F = self.n_own, H * C
         grp = self.group
         fused = fused_heads(H, C)
-        node_scores = lib.mp_gat_node_scores_f32 if fused else lib.mp_gat_node_scores_wide_f32
+        node_scores = nat.mp_gat_node_scores_f32 if fused else nat.mp_gat_node_scores_wide_f32
         xl = torch.empty((self.n_local_src, F), dtype=torch.float32, device=dev)
         xl[:n_own].copy_(xw_own)
         a_src = torch.empty((self.n_local_src, H), dtype=torch.float32, device=dev)
         a_dst = torch.empty((self.n_local_src, H), dtype=torch.float32, device=dev)
         if n_own:
-            _lib.check(node_scores(xl.data_ptr(), n_own, H, C, att_c.data_ptr(), a_src.data_ptr(), a_dst.data_ptr(),
-                                   st), "mp_gat_node_scores (own rows)")
+            node_scores(xl.data_ptr(), n_own, H, C, att_c.data_ptr(), a_src.data_ptr(), a_dst.data_ptr(), st)
         # 1. a_dst of the rows the peers push pieces of
         a2a = _a2a if exchange else (lambda o, *a: o.zero_())
         adst_in = torch.empty((sum(self.adst_recv_counts), H), dtype=torch.float32, device=dev)
@@ -224,16 +223,13 @@ class GatHaloCover:
             send_s2 = torch.zeros((self.n_send, H), dtype=torch.float32, device=dev)
             if self.push_src.numel():
                 gp = g_push.dst.struct("other")
-                sb = lib.mp_gat_train_slab_bytes(gp, H, C)
+                sb = nat.mp_gat_train_slab_bytes(gp, H, C)
                 slab = torch.empty(sb, dtype=torch.uint8, device=dev)
-                _lib.check(lib.mp_gat_aggregate_train_drop_f32(gp, xl.data_ptr(), a_src.data_ptr(),
-                                                               send_adst.data_ptr(), att_c.data_ptr(), H, C,
-                                                               float(slope), None, send.data_ptr(), F, None,
-                                                               send_st.data_ptr(), send2.data_ptr(),
-                                                               send_s2.data_ptr(), int(drop[0]), float(drop[1]),
-                                                               g_push.drop_ids("dst").data_ptr(), slab.data_ptr(), sb,
-                                                               _lib.MP_STAGE_ALL, st),
-                           "mp_gat_aggregate_train_drop_f32 (pushed pieces)")
+                nat.mp_gat_aggregate_train_drop_f32(gp, xl.data_ptr(), a_src.data_ptr(), send_adst.data_ptr(),
+                                                    att_c.data_ptr(), H, C, float(slope), None, send.data_ptr(), F,
+                                                    None, send_st.data_ptr(), send2.data_ptr(), send_s2.data_ptr(),
+                                                    int(drop[0]), float(drop[1]), g_push.drop_ids("dst").data_ptr(),
+                                                    slab.data_ptr(), sb, _lib.MP_STAGE_ALL, st)
                 del slab
             else:
                 send.zero_()
@@ -245,28 +241,25 @@ class GatHaloCover:
             if train and not fused:
                 send2 = torch.empty((self.n_send, F), dtype=torch.float32, device=dev)
                 send_s2 = torch.empty((self.n_send, H), dtype=torch.float32, device=dev)
-                sb = lib.mp_gat_train_slab_bytes(gs, H, C)
+                sb = nat.mp_gat_train_slab_bytes(gs, H, C)
                 slab = torch.empty(sb, dtype=torch.uint8, device=dev)
-                _lib.check(lib.mp_gat_aggregate_train_f32(gs, xl.data_ptr(), a_src.data_ptr(), send_adst.data_ptr(),
-                                                          att_c.data_ptr(), H, C, float(slope), None, send.data_ptr(),
-                                                          F, None, send_st.data_ptr(), send2.data_ptr(),
-                                                          send_s2.data_ptr(), slab.data_ptr(), sb, _lib.MP_STAGE_ALL,
-                                                          st), "mp_gat_aggregate_train_f32 (send rows)")
+                nat.mp_gat_aggregate_train_f32(gs, xl.data_ptr(), a_src.data_ptr(), send_adst.data_ptr(),
+                                               att_c.data_ptr(), H, C, float(slope), None, send.data_ptr(), F, None,
+                                               send_st.data_ptr(), send2.data_ptr(), send_s2.data_ptr(),
+                                               slab.data_ptr(), sb, _lib.MP_STAGE_ALL, st)
             else:
-                sb = lib.mp_gat_slab_bytes(gs, H, C)
+                sb = nat.mp_gat_slab_bytes(gs, H, C)
                 slab = torch.empty(sb, dtype=torch.uint8, device=dev)
-                _lib.check(lib.mp_gat_aggregate_att_f32(gs, xl.data_ptr(), a_src.data_ptr(), send_adst.data_ptr(),
-                                                        att_c.data_ptr(), H, C, float(slope), None, send.data_ptr(),
-                                                        F, send_st.data_ptr(), slab.data_ptr(), sb, _lib.MP_STAGE_ALL,
-                                                        st), "mp_gat_aggregate_att_f32 (send rows)")
+                nat.mp_gat_aggregate_att_f32(gs, xl.data_ptr(), a_src.data_ptr(), send_adst.data_ptr(),
+                                             att_c.data_ptr(), H, C, float(slope), None, send.data_ptr(), F,
+                                             send_st.data_ptr(), slab.data_ptr(), sb, _lib.MP_STAGE_ALL, st)
             del slab
         r_st = torch.empty((self.n_halo, H, 2), dtype=torch.float32, device=dev)
         a2a(xl[n_own:], send, self.recv_counts, self.send_counts, grp)
         a2a(r_st, send_st, self.recv_counts, self.send_counts, grp)
         if self.n_halo:
-            _lib.check(node_scores(xl[n_own:].data_ptr(), self.n_halo, H, C, att_c.data_ptr(),
-                                   a_src[n_own:].data_ptr(), a_dst[n_own:].data_ptr(), st),
-                       "mp_gat_node_scores (received rows)")
+            node_scores(xl[n_own:].data_ptr(), self.n_halo, H, C, att_c.data_ptr(), a_src[n_own:].data_ptr(),
+                        a_dst[n_own:].data_ptr(), st)
         # 3. the local piece (no bias: the merge adds it)
         out = torch.empty((n_own, F), dtype=torch.float32, device=dev)
         stats = torch.empty((n_own, H, 2), dtype=torch.float32, device=dev)
@@ -276,45 +269,37 @@ class GatHaloCover:
             if drop is not None:
                 agg2 = torch.empty((n_own, F), dtype=torch.float32, device=dev)
                 s2 = torch.empty((n_own, H), dtype=torch.float32, device=dev)
-                sb = lib.mp_gat_train_slab_bytes(gl, H, C)
+                sb = nat.mp_gat_train_slab_bytes(gl, H, C)
                 slab = torch.empty(sb, dtype=torch.uint8, device=dev)
-                _lib.check(lib.mp_gat_aggregate_train_drop_f32(gl, xl.data_ptr(), a_src.data_ptr(), a_dst.data_ptr(),
-                                                               att_c.data_ptr(), H, C, float(slope), None,
-                                                               out.data_ptr(), F, None, stats.data_ptr(),
-                                                               agg2.data_ptr(), s2.data_ptr(), int(drop[0]),
-                                                               float(drop[1]), g_loc.drop_ids("dst").data_ptr(),
-                                                               slab.data_ptr(), sb, _lib.MP_STAGE_ALL, st),
-                           "mp_gat_aggregate_train_drop_f32 (local piece)")
+                nat.mp_gat_aggregate_train_drop_f32(gl, xl.data_ptr(), a_src.data_ptr(), a_dst.data_ptr(),
+                                                    att_c.data_ptr(), H, C, float(slope), None, out.data_ptr(), F, None,
+                                                    stats.data_ptr(), agg2.data_ptr(), s2.data_ptr(), int(drop[0]),
+                                                    float(drop[1]), g_loc.drop_ids("dst").data_ptr(), slab.data_ptr(),
+                                                    sb, _lib.MP_STAGE_ALL, st)
             elif train:
                 agg2 = torch.empty((n_own, F), dtype=torch.float32, device=dev)
                 s2 = torch.empty((n_own, H), dtype=torch.float32, device=dev)
-                sb = lib.mp_gat_train_slab_bytes(gl, H, C)
+                sb = nat.mp_gat_train_slab_bytes(gl, H, C)
                 slab = torch.empty(sb, dtype=torch.uint8, device=dev)
-                _lib.check(lib.mp_gat_aggregate_train_f32(gl, xl.data_ptr(), a_src.data_ptr(), a_dst.data_ptr(),
-                                                          att_c.data_ptr(), H, C, float(slope), None, out.data_ptr(),
-                                                          F, None, stats.data_ptr(), agg2.data_ptr(), s2.data_ptr(),
-                                                          slab.data_ptr(), sb, _lib.MP_STAGE_ALL, st),
-                           "mp_gat_aggregate_train_f32 (local piece)")
+                nat.mp_gat_aggregate_train_f32(gl, xl.data_ptr(), a_src.data_ptr(), a_dst.data_ptr(), att_c.data_ptr(),
+                                               H, C, float(slope), None, out.data_ptr(), F, None, stats.data_ptr(),
+                                               agg2.data_ptr(), s2.data_ptr(), slab.data_ptr(), sb, _lib.MP_STAGE_ALL,
+                                               st)
             else:
-                sb = lib.mp_gat_slab_bytes(gl, H, C)
+                sb = nat.mp_gat_slab_bytes(gl, H, C)
                 slab = torch.empty(sb, dtype=torch.uint8, device=dev)
-                _lib.check(lib.mp_gat_aggregate_att_f32(gl, xl.data_ptr(), a_src.data_ptr(), a_dst.data_ptr(),
-                                                        att_c.data_ptr(), H, C, float(slope), None, out.data_ptr(), F,
-                                                        stats.data_ptr(), slab.data_ptr(), sb, _lib.MP_STAGE_ALL, st),
-                           "mp_gat_aggregate_att_f32 (local piece)")
+                nat.mp_gat_aggregate_att_f32(gl, xl.data_ptr(), a_src.data_ptr(), a_dst.data_ptr(), att_c.data_ptr(), H,
+                                             C, float(slope), None, out.data_ptr(), F, stats.data_ptr(),
+                                             slab.data_ptr(), sb, _lib.MP_STAGE_ALL, st)
             del slab
             # 4. merge the pieces (+ bias; agg2 / s2 scaled to the merged rows)
             m = g_merge.dst
             merged = self.part_row.numel() > 0
             n_parts = self.n_halo if merged else 0       # rows of the receive buffer the merge list names
-            _lib.check(lib.mp_gat_merge_partials_f32(n_own, H, C, m.rowptr.data_ptr(),
-                                                     m.col.data_ptr() if merged else None, n_parts,
-                                                     xl[n_own:].data_ptr() if merged else None,
-                                                     _lib.nbytes(xl[n_own:]), F,
-                                                     r_st.data_ptr() if merged else None, _lib.nbytes(r_st),
-                                                     _lib.ptr(bias),
-                                                     out.data_ptr(), F, stats.data_ptr(), _lib.ptr(agg2),
-                                                     _lib.ptr(s2), st), "mp_gat_merge_partials_f32")
+            nat.mp_gat_merge_partials_f32(n_own, H, C, m.rowptr.data_ptr(), m.col.data_ptr() if merged else None,
+                                          n_parts, xl[n_own:].data_ptr() if merged else None, _lib.nbytes(xl[n_own:]),
+                                          F, r_st.data_ptr() if merged else None, _lib.nbytes(r_st), _lib.ptr(bias),
+                                          out.data_ptr(), F, stats.data_ptr(), _lib.ptr(agg2), _lib.ptr(s2), st)
         saved = (xl, a_src, a_dst, stats, agg2, s2, send_st, send2, send_s2, drop, send_adst) if (train or keep) else None
         return out, saved
 
@@ -370,7 +355,7 @@ class GatHaloCover:
         forward's node scores and merged row statistics (saved of
         forward_device).  Collective over the group (two all_to_alls)."""
         from . import _lib
-        lib = _lib.load()
+        nat = _lib.native()
         xl, a_src, a_dst, stats, _, _, _, _, _, _, send_adst = saved
         dev = xl.device
         st = _lib.stream_ptr(dev)
@@ -379,9 +364,8 @@ class GatHaloCover:
         n_loc = int(self.loc_src.numel())
         if n_loc:
             a_loc = torch.empty((n_loc, H), dtype=torch.float32, device=dev)
-            _lib.check(lib.mp_gat_alpha_f32(self.loc_src.data_ptr(), self.loc_dst.data_ptr(), n_loc, H,
-                                            a_src.data_ptr(), a_dst.data_ptr(), float(slope), stats.data_ptr(),
-                                            a_loc.data_ptr(), st), "mp_gat_alpha_f32 (local piece)")
+            nat.mp_gat_alpha_f32(self.loc_src.data_ptr(), self.loc_dst.data_ptr(), n_loc, H, a_src.data_ptr(),
+                                 a_dst.data_ptr(), float(slope), stats.data_ptr(), a_loc.data_ptr(), st)
             alpha[self.loc_pos] = a_loc
         # the merged (max, denominator) of each pushed destination back to its pusher
         rev_st = torch.zeros((self.n_halo, H, 2), dtype=torch.float32, device=dev)
@@ -393,9 +377,8 @@ class GatHaloCover:
         E_push = int(self.push_src.numel())
         a_push = torch.empty((E_push, H), dtype=torch.float32, device=dev)
         if E_push:
-            _lib.check(lib.mp_gat_alpha_f32(self.push_src.data_ptr(), self.push_dst.data_ptr(), E_push, H,
-                                            a_src.data_ptr(), send_adst.data_ptr(), float(slope), back_st.data_ptr(),
-                                            a_push.data_ptr(), st), "mp_gat_alpha_f32 (pushed pieces)")
+            nat.mp_gat_alpha_f32(self.push_src.data_ptr(), self.push_dst.data_ptr(), E_push, H, a_src.data_ptr(),
+                                 send_adst.data_ptr(), float(slope), back_st.data_ptr(), a_push.data_ptr(), st)
         got = torch.empty((sum(self.push_edges_to), H), dtype=torch.float32, device=dev)
         _a2a(got, a_push, self.push_edges_to, self.push_edges_from, self.group)
         if got.shape[0]:
@@ -406,7 +389,7 @@ class GatHaloCover:
         """d xw_own, d att (or None), d bias (or None) of forward_device (see the
         module docstring for the split)."""
         from . import _lib, ops
-        lib = _lib.load()
+        nat = _lib.native()
         g_loc, _, g_merge, g_copy_t, g_push = self.graphs()
         xl, a_src, a_dst, stats, agg2, s2, send_st, send2, send_s2, drop, _ = saved
         seed, p_drop = (0, 0.0) if drop is None else (int(drop[0]), float(drop[1]))
@@ -422,20 +405,17 @@ class GatHaloCover:
             gx_out += sum alpha g + d a_src att_src; returns d a_src."""
             acc2 = torch.zeros((n_rows, F), dtype=torch.float32, device=dev)
             sc = torch.zeros((n_rows, H), dtype=torch.float32, device=dev)
-            sb = lib.mp_gat_train_slab_bytes(gt_struct, H, C)
+            sb = nat.mp_gat_train_slab_bytes(gt_struct, H, C)
             slab = torch.empty(sb, dtype=torch.uint8, device=dev)
-            _lib.check(lib.mp_gat_backward_wide_f32(gt_struct, grad_out.data_ptr(), F, a_src.data_ptr(),
-                                                    pack_.data_ptr(), H, C, float(slope), seed, p_drop,
-                                                    graph.drop_ids("src").data_ptr() if drop is not None else None,
-                                                    gx_out.data_ptr(),
-                                                    acc2.data_ptr(), _lib.nbytes(acc2), sc.data_ptr(),
-                                                    _lib.nbytes(sc), slab.data_ptr(), sb, _lib.MP_STAGE_ALL, st),
-                       "mp_gat_backward_wide_f32 (cover)")
+            nat.mp_gat_backward_wide_f32(gt_struct, grad_out.data_ptr(), F, a_src.data_ptr(), pack_.data_ptr(), H, C,
+                                         float(slope), seed, p_drop,
+                                         graph.drop_ids("src").data_ptr() if drop is not None else None,
+                                         gx_out.data_ptr(), acc2.data_ptr(), _lib.nbytes(acc2), sc.data_ptr(),
+                                         _lib.nbytes(sc), slab.data_ptr(), sb, _lib.MP_STAGE_ALL, st)
             del slab
             zero_gd = torch.zeros((n_rows, H), dtype=torch.float32, device=dev)
-            _lib.check(lib.mp_gat_backward_epilogue_wide_f32(gx_out.data_ptr(), acc2.data_ptr(), xw_rows.data_ptr(),
-                                                             att_c.data_ptr(), zero_gd.data_ptr(), sc.data_ptr(),
-                                                             n_rows, H, C, st), "mp_gat_backward_epilogue_wide_f32")
+            nat.mp_gat_backward_epilogue_wide_f32(gx_out.data_ptr(), acc2.data_ptr(), xw_rows.data_ptr(),
+                                                  att_c.data_ptr(), zero_gd.data_ptr(), sc.data_ptr(), n_rows, H, C, st)
             return sc
 
         # p: pack from the merged stats, node-wise d a_dst of the local edges
@@ -443,17 +423,13 @@ class GatHaloCover:
         ga_dst = torch.zeros((max(n_own, 1), H), dtype=torch.float32, device=dev)
         if n_own:
             if fused:
-                _lib.check(lib.mp_gat_backward_prep_train_f32(g.data_ptr(), F, out.data_ptr(), F, _lib.ptr(bias),
-                                                              agg2.data_ptr(), s2.data_ptr(), a_dst.data_ptr(),
-                                                              stats.data_ptr(), n_own, H, C, pack.data_ptr(),
-                                                              _lib.nbytes(pack), None, 0, ga_dst.data_ptr(), st),
-                           "mp_gat_backward_prep_train_f32 (cover)")
+                nat.mp_gat_backward_prep_train_f32(g.data_ptr(), F, out.data_ptr(), F, _lib.ptr(bias), agg2.data_ptr(),
+                                                   s2.data_ptr(), a_dst.data_ptr(), stats.data_ptr(), n_own, H, C,
+                                                   pack.data_ptr(), _lib.nbytes(pack), None, 0, ga_dst.data_ptr(), st)
             else:
-                _lib.check(lib.mp_gat_backward_prep_wide_f32(g.data_ptr(), F, out.data_ptr(), F, _lib.ptr(bias),
-                                                             agg2.data_ptr(), s2.data_ptr(), a_dst.data_ptr(),
-                                                             stats.data_ptr(), n_own, H, C, pack.data_ptr(),
-                                                             _lib.nbytes(pack), ga_dst.data_ptr(), st),
-                           "mp_gat_backward_prep_wide_f32 (cover)")
+                nat.mp_gat_backward_prep_wide_f32(g.data_ptr(), F, out.data_ptr(), F, _lib.ptr(bias), agg2.data_ptr(),
+                                                  s2.data_ptr(), a_dst.data_ptr(), stats.data_ptr(), n_own, H, C,
+                                                  pack.data_ptr(), _lib.nbytes(pack), ga_dst.data_ptr(), st)
         # p: the transposed pass over the local edges (the att_dst term comes last)
         gx_l = torch.zeros((nl, F), dtype=torch.float32, device=dev)
         ga_src_l = torch.zeros((nl, H), dtype=torch.float32, device=dev)
@@ -462,25 +438,21 @@ class GatHaloCover:
             gs = gt.struct("dst_slot")
             if fused and drop is not None:
                 zero_gd = torch.zeros((nl, H), dtype=torch.float32, device=dev)
-                sb = lib.mp_gat_slab_bytes(gs, H, C)
+                sb = nat.mp_gat_slab_bytes(gs, H, C)
                 slab = torch.empty(sb, dtype=torch.uint8, device=dev)
-                _lib.check(lib.mp_gat_backward_train_drop_f32(gs, g.data_ptr(), F, xl.data_ptr(), a_src.data_ptr(),
-                                                              pack.data_ptr(), att_c.data_ptr(), H, C, float(slope),
-                                                              zero_gd.data_ptr(), seed, p_drop,
-                                                              g_loc.drop_ids("src").data_ptr(), gx_l.data_ptr(),
-                                                              ga_src_l.data_ptr(), slab.data_ptr(), sb,
-                                                              _lib.MP_STAGE_ALL, st),
-                           "mp_gat_backward_train_drop_f32 (local piece)")
+                nat.mp_gat_backward_train_drop_f32(gs, g.data_ptr(), F, xl.data_ptr(), a_src.data_ptr(),
+                                                   pack.data_ptr(), att_c.data_ptr(), H, C, float(slope),
+                                                   zero_gd.data_ptr(), seed, p_drop, g_loc.drop_ids("src").data_ptr(),
+                                                   gx_l.data_ptr(), ga_src_l.data_ptr(), slab.data_ptr(), sb,
+                                                   _lib.MP_STAGE_ALL, st)
                 del slab, zero_gd
             elif fused:
                 zero_gd = torch.zeros((nl, H), dtype=torch.float32, device=dev)
-                sb = lib.mp_gat_slab_bytes(gs, H, C)
+                sb = nat.mp_gat_slab_bytes(gs, H, C)
                 slab = torch.empty(sb, dtype=torch.uint8, device=dev)
-                _lib.check(lib.mp_gat_backward_train_f32(gs, g.data_ptr(), F, xl.data_ptr(), a_src.data_ptr(),
-                                                         pack.data_ptr(), att_c.data_ptr(), H, C, float(slope),
-                                                         zero_gd.data_ptr(), gx_l.data_ptr(), ga_src_l.data_ptr(),
-                                                         slab.data_ptr(), sb, _lib.MP_STAGE_ALL, st),
-                           "mp_gat_backward_train_f32 (local piece)")
+                nat.mp_gat_backward_train_f32(gs, g.data_ptr(), F, xl.data_ptr(), a_src.data_ptr(), pack.data_ptr(),
+                                              att_c.data_ptr(), H, C, float(slope), zero_gd.data_ptr(), gx_l.data_ptr(),
+                                              ga_src_l.data_ptr(), slab.data_ptr(), sb, _lib.MP_STAGE_ALL, st)
                 del slab, zero_gd
             else:
                 ga_src_l = wide_pass(gs, nl, g, pack, xl, gx_l, g_loc)
@@ -524,13 +496,11 @@ class GatHaloCover:
             gs = gt.struct("dst_slot")
             gx_push = torch.empty((n_own, F), dtype=torch.float32, device=dev)
             de = torch.empty((E_push, H), dtype=torch.float32, device=dev)
-            sb = lib.mp_gat_slab_bytes(gs, H, C)
+            sb = nat.mp_gat_slab_bytes(gs, H, C)
             slab = torch.empty(sb, dtype=torch.uint8, device=dev)
-            _lib.check(lib.mp_gat_backward_f32(gs, back.data_ptr(), F, xl.data_ptr(), a_src.data_ptr(),
-                                               back_pack.data_ptr(), att_c.data_ptr(), H, C, float(slope),
-                                               gx_push.data_ptr(), ga_src_push.data_ptr(), de.data_ptr(),
-                                               _lib.nbytes(de), slab.data_ptr(), sb, _lib.MP_STAGE_ALL, st),
-                       "mp_gat_backward_f32 (pushed pieces)")
+            nat.mp_gat_backward_f32(gs, back.data_ptr(), F, xl.data_ptr(), a_src.data_ptr(), back_pack.data_ptr(),
+                                    att_c.data_ptr(), H, C, float(slope), gx_push.data_ptr(), ga_src_push.data_ptr(),
+                                    de.data_ptr(), _lib.nbytes(de), slab.data_ptr(), sb, _lib.MP_STAGE_ALL, st)
             del slab
             gx += gx_push
             ga_back = ops._aggregate(g_push.dst, "slot", de, None, "sum", 0, None)[0]
@@ -541,8 +511,8 @@ class GatHaloCover:
             ga_dst = ga_dst + ops._aggregate(g_merge.dst, "other", ga_in, None, "sum", 0, None)[0]
         ga_dst = ga_dst[:n_own]
         if n_own:
-            _lib.check(lib.mp_heads_outer_add_f32(gx.data_ptr(), F, ga_dst.contiguous().data_ptr(), n_own, H, C,
-                                                  att_c.data_ptr(), 2 * C, st), "mp_heads_outer_add_f32")
+            nat.mp_heads_outer_add_f32(gx.data_ptr(), F, ga_dst.contiguous().data_ptr(), n_own, H, C, att_c.data_ptr(),
+                                       2 * C, st)
         gatt = None
         if want_att:
             x_own3 = xl[:n_own].view(n_own, H, C)

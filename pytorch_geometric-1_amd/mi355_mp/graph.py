@@ -72,7 +72,7 @@ class CSR:
 
     def __init__(self, key, other, n_rows, n_other, chunk=DEFAULT_CHUNK, snap=None, target_tasks=None):
         _lib.require_device(key)
-        lib = _lib.load()
+        nat = _lib.native()
         dev = key.device
         key = key.contiguous()
         other = other.contiguous() if other is not None else None
@@ -88,11 +88,10 @@ class CSR:
         self.eid = torch.zeros(E + SLOT_PAD, dtype=torch.int32, device=dev)
         bad = torch.zeros(1, dtype=torch.int32, device=dev)
         st = _lib.stream_ptr(dev)
-        ws_bytes = lib.mp_csr_build_workspace(E, self.n_rows)
+        ws_bytes = nat.mp_csr_build_workspace(E, self.n_rows)
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        _lib.check(lib.mp_csr_build(key.data_ptr(), _lib.ptr(other), E, self.n_rows, self.n_other,
-                                    self.rowptr.data_ptr(), self.col.data_ptr(), self.eid.data_ptr(),
-                                    bad.data_ptr(), ws.data_ptr(), ws_bytes, st), "mp_csr_build")
+        nat.mp_csr_build(key.data_ptr(), _lib.ptr(other), E, self.n_rows, self.n_other, self.rowptr.data_ptr(),
+                         self.col.data_ptr(), self.eid.data_ptr(), bad.data_ptr(), ws.data_ptr(), ws_bytes, st)
         # the bad-index count is read together with the schedule's split-row count:
         # one host sync per CSR (the schedule over a rowptr that skipped bad ids is
         # still well formed, and is dropped with the raise)
@@ -102,20 +101,19 @@ class CSR:
     def _build_schedule(self, bad=None):
         """Merge-path schedule over rowptr (tasks of `chunk` rows + slots); bad:
         the CSR build's out-of-range count, read in the same host sync."""
-        lib = _lib.load()
+        nat = _lib.native()
         dev, E = self.device, self.n_edges
         st = _lib.stream_ptr(dev)
-        self.n_waves = int(lib.mp_schedule_n_waves(self.n_rows, E, self.chunk))
+        self.n_waves = int(nat.mp_schedule_n_waves(self.n_rows, E, self.chunk))
         self.wave_row = torch.empty(self.n_waves + 1, dtype=torch.int32, device=dev)
         self.wave_slot = torch.empty(self.n_waves + 1, dtype=torch.int32, device=dev)
         self.split_waves = torch.empty(self.n_waves, dtype=torch.int32, device=dev)
         n_split = torch.zeros(1, dtype=torch.int32, device=dev)
-        sws = lib.mp_schedule_workspace(self.n_waves)
+        sws = nat.mp_schedule_workspace(self.n_waves)
         ws = torch.empty(sws, dtype=torch.uint8, device=dev)
-        _lib.check(lib.mp_schedule_build(self.rowptr.data_ptr(), self.n_rows, E, self.chunk, self.snap,
-                                         self.wave_row.data_ptr(), self.wave_slot.data_ptr(),
-                                         self.split_waves.data_ptr(), n_split.data_ptr(),
-                                         ws.data_ptr(), sws, st), "mp_schedule_build")
+        nat.mp_schedule_build(self.rowptr.data_ptr(), self.n_rows, E, self.chunk, self.snap, self.wave_row.data_ptr(),
+                              self.wave_slot.data_ptr(), self.split_waves.data_ptr(), n_split.data_ptr(), ws.data_ptr(),
+                              sws, st)
         if bad is None:
             self.n_split = int(n_split.item())
         else:
@@ -218,8 +216,7 @@ class CSR:
         """int32 [E]: the row owning each CSR slot (cached)."""
         if getattr(self, "_slot_rows", None) is None:
             sr = torch.empty(max(self.n_edges, 1), dtype=torch.int32, device=self.device)
-            _lib.check(_lib.load().mp_csr_slot_rows(self.struct("other"), sr.data_ptr(),
-                                                    _lib.stream_ptr(self.device)), "mp_csr_slot_rows")
+            _lib.native().mp_csr_slot_rows(self.struct("other"), sr.data_ptr(), _lib.stream_ptr(self.device))
             self._slot_rows = sr
         return self._slot_rows
 
@@ -227,8 +224,7 @@ class CSR:
         """int32 [E]: inv[e] = the slot of edge id e in this CSR (cached)."""
         if getattr(self, "_inv", None) is None:
             inv = torch.empty(max(self.n_edges, 1), dtype=torch.int32, device=self.device)
-            _lib.check(_lib.load().mp_csr_inverse_eid(self.struct("other"), inv.data_ptr(),
-                                                      _lib.stream_ptr(self.device)), "mp_csr_inverse_eid")
+            _lib.native().mp_csr_inverse_eid(self.struct("other"), inv.data_ptr(), _lib.stream_ptr(self.device))
             self._inv = inv
         return self._inv
 
@@ -241,14 +237,13 @@ class CSR:
 
     def to_csr_order(self, edge_values):
         """Permute a per-edge fp32 vector (original order) into CSR slot order."""
-        lib = _lib.load()
+        nat = _lib.native()
         edge_values = edge_values.contiguous()
         out = torch.zeros(edge_values.numel() + SLOT_PAD, dtype=edge_values.dtype,
                           device=edge_values.device)[:edge_values.numel()]
         if self.n_edges:
-            _lib.check(lib.mp_permute_f32(edge_values.data_ptr(), self.eid.data_ptr(), self.n_edges,
-                                          out.data_ptr(), _lib.stream_ptr(self.device)),
-                       "mp_permute_f32")
+            nat.mp_permute_f32(edge_values.data_ptr(), self.eid.data_ptr(), self.n_edges, out.data_ptr(),
+                               _lib.stream_ptr(self.device))
         return out
 
 

@@ -37,7 +37,7 @@ def _any_2d(x, what):
 def _aggregate_any(csr, gather, src, reduce, flags, out=None):
     """mp_segment_reduce: any supported dtype, every row in edge order (not
     split).  Returns (out, arg_or_None)."""
-    lib = _lib.load()
+    nat = _lib.native()
     F = src.shape[1]
     dev = src.device
     if out is None:
@@ -45,9 +45,9 @@ def _aggregate_any(csr, gather, src, reduce, flags, out=None):
     arg = torch.empty((csr.n_rows, F), dtype=torch.int64, device=dev) if reduce in ("max", "min") else None
     if csr.n_rows == 0 or F == 0:
         return out, arg
-    _lib.check(lib.mp_segment_reduce(csr.struct(gather), _lib.MP_DTYPE[src.dtype], src.data_ptr(), src.stride(0), F,
-                                     _lib.MP_REDUCE[reduce], flags, out.data_ptr(), out.stride(0), _lib.ptr(arg),
-                                     _lib.stream_ptr(dev)), "mp_segment_reduce")
+    nat.mp_segment_reduce(csr.struct(gather), _lib.MP_DTYPE[src.dtype], src.data_ptr(), src.stride(0), F,
+                          _lib.MP_REDUCE[reduce], flags, out.data_ptr(), out.stride(0), _lib.ptr(arg),
+                          _lib.stream_ptr(dev))
     return out, arg
 
 
@@ -80,7 +80,7 @@ def _max_csr(csr):
 def _aggregate(csr, gather, x, w_csr, reduce, flags, bias, out=None, stages=_lib.MP_STAGE_ALL, slab=None,
                arg=None):
     """Launch mp_aggregate_f32; returns (out, arg_or_None)."""
-    lib = _lib.load()
+    nat = _lib.native()
     if reduce in ("max", "min") and w_csr is None and gather == "other" and stages == _lib.MP_STAGE_ALL:
         csr = _max_csr(csr)
     F = x.shape[1]
@@ -94,13 +94,11 @@ def _aggregate(csr, gather, x, w_csr, reduce, flags, bias, out=None, stages=_lib
         return out, arg
     g = csr.struct(gather)
     red = _lib.MP_REDUCE[reduce]
-    sb = lib.mp_aggregate_slab_bytes(g, F, red)
+    sb = nat.mp_aggregate_slab_bytes(g, F, red)
     if slab is None or slab.numel() < sb:
         slab = torch.empty(sb, dtype=torch.uint8, device=dev)
-    _lib.check(lib.mp_aggregate_f32(g, _lib.ptr(w_csr), x.data_ptr(), x.stride(0), F, red, flags,
-                                    _lib.ptr(bias), out.data_ptr(), out.stride(0), _lib.ptr(arg),
-                                    slab.data_ptr(), sb, stages, _lib.stream_ptr(dev)),
-               "mp_aggregate_f32")
+    nat.mp_aggregate_f32(g, _lib.ptr(w_csr), x.data_ptr(), x.stride(0), F, red, flags, _lib.ptr(bias), out.data_ptr(),
+                         out.stride(0), _lib.ptr(arg), slab.data_ptr(), sb, stages, _lib.stream_ptr(dev))
     return out, arg
 
 
@@ -114,41 +112,38 @@ def aggregate_tiles(csr, gather, x, w_csr, F, out, reduce="sum", flags=0, bias=N
     flags -- the bias goes only to rows whose flag is nonzero.  Bitwise the
     arithmetic of _aggregate on the same values laid out row-major.  Returns
     out."""
-    lib = _lib.load()
+    nat = _lib.native()
     dev = out.device
     if csr.n_rows == 0:
         return out
     g = csr.struct(gather)
     red = _lib.MP_REDUCE[reduce]
-    sb = lib.mp_aggregate_slab_bytes(g, F, red)
+    sb = nat.mp_aggregate_slab_bytes(g, F, red)
     if slab is None or slab.numel() < sb:
         slab = torch.empty(sb, dtype=torch.uint8, device=dev)
     xw, xs = x_tiles if x_tiles is not None else (0, 0)
     ow, os_ = out_tiles if out_tiles is not None else (0, 0)
     ldx = 0 if x_tiles is not None else x.stride(0)
     ldo = 0 if out_tiles is not None else out.stride(0)
-    _lib.check(lib.mp_aggregate_tiles_f32(g, _lib.ptr(w_csr), x.data_ptr() if x.numel() else None, ldx, xw, xs, F, red,
-                                          flags, _lib.ptr(bias), _lib.ptr(bias_rows), out.data_ptr(), ldo, ow, os_,
-                                          slab.data_ptr(), sb,
-                                          stages, _lib.stream_ptr(dev)), "mp_aggregate_tiles_f32")
+    nat.mp_aggregate_tiles_f32(g, _lib.ptr(w_csr), x.data_ptr() if x.numel() else None, ldx, xw, xs, F, red, flags,
+                               _lib.ptr(bias), _lib.ptr(bias_rows), out.data_ptr(), ldo, ow, os_, slab.data_ptr(), sb,
+                               stages, _lib.stream_ptr(dev))
     return out
 
 
 def gather_rows(x, idx):
     """out = x[idx] via the native row gather (no autograd; see GatherRows)."""
-    lib = _lib.load()
+    nat = _lib.native()
     x = _any_2d(x, "x")
     idx = idx.to(torch.int64).contiguous()
     out = torch.empty((idx.numel(), x.shape[1]), dtype=x.dtype, device=x.device)
     if idx.numel() and x.shape[1]:
         if x.dtype == torch.float32:
-            _lib.check(lib.mp_gather_rows_f32(x.data_ptr(), x.stride(0), idx.data_ptr(), idx.numel(),
-                                              x.shape[1], out.data_ptr(), out.stride(0),
-                                              _lib.stream_ptr(x.device)), "mp_gather_rows_f32")
+            nat.mp_gather_rows_f32(x.data_ptr(), x.stride(0), idx.data_ptr(), idx.numel(), x.shape[1], out.data_ptr(),
+                                   out.stride(0), _lib.stream_ptr(x.device))
         else:
-            _lib.check(lib.mp_gather_rows_any(x.element_size(), x.data_ptr(), x.stride(0), idx.data_ptr(),
-                                              idx.numel(), x.shape[1], out.data_ptr(), out.stride(0),
-                                              _lib.stream_ptr(x.device)), "mp_gather_rows_any")
+            nat.mp_gather_rows_any(x.element_size(), x.data_ptr(), x.stride(0), idx.data_ptr(), idx.numel(), x.shape[1],
+                                   out.data_ptr(), out.stride(0), _lib.stream_ptr(x.device))
     return out
 
 
@@ -159,10 +154,10 @@ def col_sums(g):
     n, F = g.shape
     if g.is_cuda and 0 < F <= 256 and F % 4 == 0 and g.stride(1) == 1 and g.stride(0) % 4 == 0 \
             and g.data_ptr() % 16 == 0 and g.dtype == torch.float32:
-        lib = _lib.load()
-        part = torch.empty((int(lib.mp_gat_bwd_blocks(n)), F), dtype=torch.float32, device=g.device)
-        _lib.check(lib.mp_col_sums_f32(g.data_ptr(), g.stride(0), n, F, part.data_ptr(), _lib.nbytes(part),
-                                       _lib.stream_ptr(g.device)), "mp_col_sums_f32")
+        nat = _lib.native()
+        part = torch.empty((int(nat.mp_gat_bwd_blocks(n)), F), dtype=torch.float32, device=g.device)
+        nat.mp_col_sums_f32(g.data_ptr(), g.stride(0), n, F, part.data_ptr(), _lib.nbytes(part),
+                            _lib.stream_ptr(g.device))
         return part.sum(0)
     return g.sum(0)
 
@@ -176,34 +171,30 @@ def arg_backward(graph, arg, g, n_src, edge_weight=None, x=None, want_gx=True, w
     transposed CSR that adds each source row's winning terms slot by slot
     (mp_scatter_arg_backward_csr_f32) -- no float atomics.  `arg` holds original
     edge ids of graph.dst's edges (E = no edge).  Returns (gx or None, gw or None)."""
-    lib = _lib.load()
+    nat = _lib.native()
     dev = g.device
     st = _lib.stream_ptr(dev)
     src = graph.src
     E = src.n_edges
     F = g.shape[1]
     inv = src.inverse_eid()
-    W = int(lib.mp_arg_mask_words(F))
+    W = int(nat.mp_arg_mask_words(F))
     mask = torch.empty(max(E * W, 2), dtype=torch.int32, device=dev)
-    _lib.check(lib.mp_arg_winner_mask(arg.data_ptr(), g.shape[0], F, E, inv.data_ptr(), mask.data_ptr(),
-                                      _lib.nbytes(mask), st), "mp_arg_winner_mask")
+    nat.mp_arg_winner_mask(arg.data_ptr(), g.shape[0], F, E, inv.data_ptr(), mask.data_ptr(), _lib.nbytes(mask), st)
     w = edge_weight.to(torch.float32).contiguous() if edge_weight is not None else None
     gx = gw = None
     if want_gx:
         gx = torch.empty((int(n_src), F), dtype=torch.float32, device=dev)
-        _lib.check(lib.mp_scatter_arg_backward_csr_f32(src.struct("other"), mask.data_ptr(), _lib.nbytes(mask),
-                                                       g.data_ptr(), g.stride(0), F, _lib.ptr(w), gx.data_ptr(),
-                                                       gx.stride(0), st),
-                   "mp_scatter_arg_backward_csr_f32")
+        nat.mp_scatter_arg_backward_csr_f32(src.struct("other"), mask.data_ptr(), _lib.nbytes(mask), g.data_ptr(),
+                                            g.stride(0), F, _lib.ptr(w), gx.data_ptr(), gx.stride(0), st)
     if want_gw:
         ei = graph._edge_index()
         srcs = ei[graph.j].contiguous()
         dsts = ei[graph.i].contiguous()
         gw = torch.empty(max(E, 1), dtype=torch.float32, device=dev)[:E]
-        _lib.check(lib.mp_scatter_arg_grad_w_f32(srcs.data_ptr(), dsts.data_ptr(), E, inv.data_ptr(), mask.data_ptr(),
-                                                 _lib.nbytes(mask), F, g.data_ptr(), g.stride(0), x.data_ptr(),
-                                                 x.stride(0),
-                                                 gw.data_ptr(), st), "mp_scatter_arg_grad_w_f32")
+        nat.mp_scatter_arg_grad_w_f32(srcs.data_ptr(), dsts.data_ptr(), E, inv.data_ptr(), mask.data_ptr(),
+                                      _lib.nbytes(mask), F, g.data_ptr(), g.stride(0), x.data_ptr(), x.stride(0),
+                                      gw.data_ptr(), st)
     return gx, gw
 
 
@@ -279,9 +270,8 @@ def _edge_dot(csr, g, x):
         return out
     sr = csr.slot_rows()
     d = torch.empty(E, dtype=torch.float32, device=dev)
-    _lib.check(_lib.load().mp_gat_sddmm_f32(csr.struct("other"), sr.data_ptr(), g.data_ptr(), g.stride(0),
-                                            x.data_ptr(), x.stride(0), 1, F, d.data_ptr(), _lib.stream_ptr(dev)),
-               "mp_gat_sddmm_f32")
+    _lib.native().mp_gat_sddmm_f32(csr.struct("other"), sr.data_ptr(), g.data_ptr(), g.stride(0), x.data_ptr(),
+                                   x.stride(0), 1, F, d.data_ptr(), _lib.stream_ptr(dev))
     out[csr.eid[:E].long()] = d
     return out
 
@@ -333,17 +323,15 @@ class _SegmentReduce(torch.autograd.Function):
         grad_out = grad_out.contiguous()
         reduce = ctx.reduce
         if reduce in ("max", "min"):
-            lib = _lib.load()
+            nat = _lib.native()
             g = (grad_out * keep if keep is not None else grad_out).contiguous()
             gs = torch.zeros((ctx.n_src, g.shape[1]), dtype=g.dtype, device=g.device)
             if g.dtype == torch.float32:
-                _lib.check(lib.mp_scatter_arg_backward_f32(g.data_ptr(), arg.data_ptr(), g.shape[0], g.shape[1],
-                                                           ctx.n_src, gs.data_ptr(), gs.stride(0),
-                                                           _lib.stream_ptr(g.device)), "mp_scatter_arg_backward_f32")
+                nat.mp_scatter_arg_backward_f32(g.data_ptr(), arg.data_ptr(), g.shape[0], g.shape[1], ctx.n_src,
+                                                gs.data_ptr(), gs.stride(0), _lib.stream_ptr(g.device))
             else:
-                _lib.check(lib.mp_scatter_arg_any(g.element_size(), g.data_ptr(), arg.data_ptr(), g.shape[0],
-                                                  g.shape[1], ctx.n_src, gs.data_ptr(), gs.stride(0),
-                                                  _lib.stream_ptr(g.device)), "mp_scatter_arg_any")
+                nat.mp_scatter_arg_any(g.element_size(), g.data_ptr(), arg.data_ptr(), g.shape[0], g.shape[1],
+                                       ctx.n_src, gs.data_ptr(), gs.stride(0), _lib.stream_ptr(g.device))
             return gs, None, None, None, None
         g = grad_out
         if reduce == "mean":
@@ -399,16 +387,14 @@ class _SegmentReduceInto(torch.autograd.Function):
         index, arg = ctx.saved_tensors
         g = g.contiguous()
         if ctx.reduce in ("max", "min"):
-            lib = _lib.load()
+            nat = _lib.native()
             gs = torch.zeros((ctx.n_src, g.shape[1]), dtype=g.dtype, device=g.device)
             if g.dtype == torch.float32:
-                _lib.check(lib.mp_scatter_arg_backward_f32(g.data_ptr(), arg.data_ptr(), g.shape[0], g.shape[1],
-                                                           ctx.n_src, gs.data_ptr(), gs.stride(0),
-                                                           _lib.stream_ptr(g.device)), "mp_scatter_arg_backward_f32")
+                nat.mp_scatter_arg_backward_f32(g.data_ptr(), arg.data_ptr(), g.shape[0], g.shape[1], ctx.n_src,
+                                                gs.data_ptr(), gs.stride(0), _lib.stream_ptr(g.device))
             else:
-                _lib.check(lib.mp_scatter_arg_any(g.element_size(), g.data_ptr(), arg.data_ptr(), g.shape[0],
-                                                  g.shape[1], ctx.n_src, gs.data_ptr(), gs.stride(0),
-                                                  _lib.stream_ptr(g.device)), "mp_scatter_arg_any")
+                nat.mp_scatter_arg_any(g.element_size(), g.data_ptr(), arg.data_ptr(), g.shape[0], g.shape[1],
+                                       ctx.n_src, gs.data_ptr(), gs.stride(0), _lib.stream_ptr(g.device))
             return gs, None, None, None
         if ctx.reduce == "mean":
             g = g / ctx.csr.degree().clamp(min=1).to(g.dtype).view(-1, 1)
@@ -522,7 +508,7 @@ def self_loops(edge_index, num_nodes, mode):
     number of self loops (the output size), like upstream's boolean-mask
     indexing."""
     _lib.require_device(edge_index)
-    lib = _lib.load()
+    nat = _lib.native()
     dev = edge_index.device
     st = _lib.stream_ptr(dev)
     N = int(num_nodes)
@@ -533,8 +519,7 @@ def self_loops(edge_index, num_nodes, mode):
     n_kept = E
     if m != _lib.MP_LOOPS_ADD and E:
         cnt = torch.empty(2, dtype=torch.int64, device=dev)
-        _lib.check(lib.mp_self_loop_count(row.data_ptr(), col.data_ptr(), E, N, cnt.data_ptr(), st),
-                   "mp_self_loop_count")
+        nat.mp_self_loop_count(row.data_ptr(), col.data_ptr(), E, N, cnt.data_ptr(), st)
         n_loops, n_bad = cnt.tolist()
         if n_bad and m == _lib.MP_LOOPS_ADD_REMAINING:
             # upstream: loop_weight[row[inv_mask]] = ... raises for these
@@ -543,10 +528,10 @@ def self_loops(edge_index, num_nodes, mode):
     n_out = n_kept + (0 if m == _lib.MP_LOOPS_REMOVE else N)
     out = torch.empty((2, n_out), dtype=torch.int64, device=dev)
     pos = torch.empty(max(n_out, 1), dtype=torch.int64, device=dev)
-    wsb = lib.mp_self_loops_workspace(E, N)
+    wsb = nat.mp_self_loops_workspace(E, N)
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    _lib.check(lib.mp_self_loops(row.data_ptr(), col.data_ptr(), E, N, m, n_kept, out[0].data_ptr(),
-                                 out[1].data_ptr(), pos.data_ptr(), ws.data_ptr(), wsb, st), "mp_self_loops")
+    nat.mp_self_loops(row.data_ptr(), col.data_ptr(), E, N, m, n_kept, out[0].data_ptr(), out[1].data_ptr(),
+                      pos.data_ptr(), ws.data_ptr(), wsb, st)
     return out, pos[:n_out]
 
 
@@ -559,8 +544,8 @@ class _GatherFill(torch.autograd.Function):
         ctx.n = w.shape[0]
         ctx.save_for_backward(pos)
         out = torch.empty(pos.shape[0], dtype=torch.float32, device=w.device)
-        _lib.check(_lib.load().mp_gather_fill_f32(w.data_ptr(), pos.data_ptr(), pos.shape[0], float(fill),
-                                                  out.data_ptr(), _lib.stream_ptr(w.device)), "mp_gather_fill_f32")
+        _lib.native().mp_gather_fill_f32(w.data_ptr(), pos.data_ptr(), pos.shape[0], float(fill), out.data_ptr(),
+                                         _lib.stream_ptr(w.device))
         return out
 
     @staticmethod
@@ -594,9 +579,8 @@ def segment_sum_serial(csr, values, out=None):
     v = values.to(torch.float32).contiguous()
     if out is None:
         out = torch.empty(max(csr.n_rows, 1), dtype=torch.float32, device=v.device)[:csr.n_rows]
-    _lib.check(_lib.load().mp_segment_sum_serial_f32(csr.rowptr.data_ptr(), csr.eid.data_ptr(), v.data_ptr(),
-                                                     csr.n_rows, out.data_ptr(), _lib.stream_ptr(v.device)),
-               "mp_segment_sum_serial_f32")
+    _lib.native().mp_segment_sum_serial_f32(csr.rowptr.data_ptr(), csr.eid.data_ptr(), v.data_ptr(), csr.n_rows,
+                                            out.data_ptr(), _lib.stream_ptr(v.device))
     return out
 
 
@@ -616,9 +600,8 @@ def norm_from_degree(row, col, deg, edge_weight, trusted=False):
     norm = torch.empty(E, dtype=torch.float32, device=row.device)
     d = deg.to(torch.float32).contiguous()
     row, col = row.contiguous(), col.contiguous()  # named: a temporary copy could be freed before the launch
-    _lib.check(_lib.load().mp_gcn_norm_from_deg_f32(row.data_ptr(), col.data_ptr(),
-                                                    _lib.ptr(w), E, d.numel(), d.data_ptr(), norm.data_ptr(),
-                                                    _lib.stream_ptr(row.device)), "mp_gcn_norm_from_deg_f32")
+    _lib.native().mp_gcn_norm_from_deg_f32(row.data_ptr(), col.data_ptr(), _lib.ptr(w), E, d.numel(), d.data_ptr(),
+                                           norm.data_ptr(), _lib.stream_ptr(row.device))
     return norm
 
 
@@ -634,7 +617,7 @@ def gcn_norm_weights(edge_index, num_nodes, edge_weight=None, integer_weights=Fa
     deterministic; that CSR is the one the layer's backward uses anyway.
     """
     _lib.require_device(edge_index, edge_weight)
-    lib = _lib.load()
+    nat = _lib.native()
     E = edge_index.shape[1]
     N = int(num_nodes)
     # the degree kernel adds at deg[row[e]]: a node id outside [0, N) raises
@@ -648,14 +631,13 @@ def gcn_norm_weights(edge_index, num_nodes, edge_weight=None, integer_weights=Fa
     deg = torch.empty(max(N, 1), dtype=torch.float32, device=dev)
     norm = torch.empty(E, dtype=torch.float32, device=dev)
     if w is None or integer_weights or E == 0:
-        _lib.check(lib.mp_gcn_norm_f32(row.data_ptr(), col.data_ptr(), _lib.ptr(w), E, N,
-                                       deg.data_ptr(), norm.data_ptr(), st), "mp_gcn_norm_f32")
+        nat.mp_gcn_norm_f32(row.data_ptr(), col.data_ptr(), _lib.ptr(w), E, N, deg.data_ptr(), norm.data_ptr(), st)
         return norm
     from .graph import graph_for
     rows = graph_for(edge_index, N, N, "source_to_target").src   # CSR keyed on edge_index[0]
     segment_sum_serial(rows, w, out=deg[:N])
-    _lib.check(lib.mp_gcn_norm_from_deg_f32(row.data_ptr(), col.data_ptr(), w.data_ptr(), E, N, deg.data_ptr(),
-                                            norm.data_ptr(), st), "mp_gcn_norm_from_deg_f32")
+    nat.mp_gcn_norm_from_deg_f32(row.data_ptr(), col.data_ptr(), w.data_ptr(), E, N, deg.data_ptr(), norm.data_ptr(),
+                                 st)
     return norm
 
 
@@ -677,7 +659,7 @@ GAT_OWN_A_SRC = True
 
 
 def gat_two_pass(csr, H, C):
-    return GAT_TWO_PASS and bool(_lib.load().mp_gat_two_pass_ok(H, C))
+    return GAT_TWO_PASS and bool(_lib.native().mp_gat_two_pass_ok(H, C))
 
 
 # Training forward: the fused pass also leaves sum_j alpha leaky' xw_j and
@@ -696,7 +678,7 @@ GAT_NODE_SCORES_IN_KERNEL_TRAIN = os.environ.get("MP_GAT_ND_TRAIN", "0") == "1"
 
 
 def _gat_nd_ok(graph, xw, H, C, bias):
-    return (GAT_NODE_SCORES_IN_KERNEL and GAT_OWN_A_SRC and bool(_lib.load().mp_gat_train_ok(H, C))
+    return (GAT_NODE_SCORES_IN_KERNEL and GAT_OWN_A_SRC and bool(_lib.native().mp_gat_train_ok(H, C))
             and not gat_two_pass(graph.dst, H, C) and xw.data_ptr() % 16 == 0 and graph.n_dst == xw.shape[0]
             and graph.n_src == xw.shape[0] and (bias is None or bias.data_ptr() % 16 == 0))
 
@@ -731,7 +713,7 @@ def gat_wide_ok(H, C):
     """Heads of any width with C % 4 == 0 (GATConv pads C to it): the fused
     training forward reads a_src from the node-score array when C/4 is not a
     power of two <= 64, and the backward runs the wide form (mp_gat_backward_wide_f32)."""
-    return bool(_lib.load().mp_gat_wide_ok(H, C))
+    return bool(_lib.native().mp_gat_wide_ok(H, C))
 
 
 def gat_dropout_ok(H, C, p):
@@ -747,14 +729,13 @@ def gat_dropout_keep(graph, seed, p, H):
     the fused GAT kernels apply for (seed, p): mp_gat_dropout_keep over the
     destination-CSR slots with their keys (Graph.drop_ids), mapped back through
     the CSR's edge ids."""
-    lib = _lib.load()
+    nat = _lib.native()
     csr = graph.dst
     E = csr.n_edges
     dev = csr.rowptr.device
     bits = torch.empty(max(E, 1), dtype=torch.int32, device=dev)
-    _lib.check(lib.mp_gat_dropout_keep(int(seed) & 0xFFFFFFFFFFFFFFFF, float(p), int(H), E,
-                                       graph.drop_ids("dst").data_ptr(), bits.data_ptr(),
-                                       _lib.stream_ptr(dev)), "mp_gat_dropout_keep")
+    nat.mp_gat_dropout_keep(int(seed) & 0xFFFFFFFFFFFFFFFF, float(p), int(H), E, graph.drop_ids("dst").data_ptr(),
+                            bits.data_ptr(), _lib.stream_ptr(dev))
     shifts = torch.arange(H, dtype=torch.int32, device=dev)
     keep_slot = ((bits[:E].unsqueeze(1) >> shifts) & 1).bool()
     keep = torch.empty_like(keep_slot)
@@ -768,7 +749,7 @@ def _gat_forward(graph, edge_index, xw, att, H, C, slope, bias, want_alpha, trai
     extra = (agg2, s2); else extra = None.  No pre-bias copy of the aggregate
     is written: the backward prologues take rs over out - bias (ABI 6).
     drop = (seed, p): attention dropout on the messages (train2 only)."""
-    lib = _lib.load()
+    nat = _lib.native()
     dev = xw.device
     N = xw.shape[0]
     csr = graph.dst
@@ -784,8 +765,7 @@ def _gat_forward(graph, edge_index, xw, att, H, C, slope, bias, want_alpha, trai
     nd = (_gat_nd_ok(graph, xw, H, C, bias) and (GAT_NODE_SCORES_IN_KERNEL_TRAIN or not train2)
           and drop is None)
     if N and not nd:
-        _lib.check(lib.mp_gat_node_scores_f32(xw.data_ptr(), N, H, C, att_c.data_ptr(), a_src.data_ptr(),
-                                              a_dst.data_ptr(), st), "mp_gat_node_scores_f32")
+        nat.mp_gat_node_scores_f32(xw.data_ptr(), N, H, C, att_c.data_ptr(), a_src.data_ptr(), a_dst.data_ptr(), st)
     out = torch.empty((graph.n_dst, H * C), dtype=torch.float32, device=dev)
     stats = torch.empty((graph.n_dst, H, 2), dtype=torch.float32, device=dev)
     g = csr.struct("other")
@@ -793,77 +773,70 @@ def _gat_forward(graph, edge_index, xw, att, H, C, slope, bias, want_alpha, trai
     if train2 and nd:
         agg2 = torch.empty((graph.n_dst, H * C), dtype=torch.float32, device=dev)
         s2 = torch.empty((graph.n_dst, H), dtype=torch.float32, device=dev)
-        sb = lib.mp_gat_train_slab_bytes(g, H, C)
+        sb = nat.mp_gat_train_slab_bytes(g, H, C)
         slab = torch.empty(sb, dtype=torch.uint8, device=dev)
-        _lib.check(lib.mp_gat_forward_train_f32(g, xw.data_ptr(), att_c.data_ptr(), H, C, float(slope), _lib.ptr(bias),
-                                                out.data_ptr(), out.stride(0), None, stats.data_ptr(),
-                                                agg2.data_ptr(), s2.data_ptr(), a_src.data_ptr(), a_dst.data_ptr(),
-                                                slab.data_ptr(), sb, _lib.MP_STAGE_ALL, st), "mp_gat_forward_train_f32")
+        nat.mp_gat_forward_train_f32(g, xw.data_ptr(), att_c.data_ptr(), H, C, float(slope), _lib.ptr(bias),
+                                     out.data_ptr(), out.stride(0), None, stats.data_ptr(), agg2.data_ptr(),
+                                     s2.data_ptr(), a_src.data_ptr(), a_dst.data_ptr(), slab.data_ptr(), sb,
+                                     _lib.MP_STAGE_ALL, st)
         extra = (agg2, s2)
     elif train2:
         agg2 = torch.empty((graph.n_dst, H * C), dtype=torch.float32, device=dev)
         s2 = torch.empty((graph.n_dst, H), dtype=torch.float32, device=dev)
-        sb = lib.mp_gat_train_slab_bytes(g, H, C)
+        sb = nat.mp_gat_train_slab_bytes(g, H, C)
         slab = torch.empty(sb, dtype=torch.uint8, device=dev)
         if drop is not None:
-            _lib.check(lib.mp_gat_aggregate_train_drop_f32(g, xw.data_ptr(), a_src.data_ptr(), a_dst.data_ptr(),
-                                                           att_c.data_ptr(), H, C, float(slope), _lib.ptr(bias),
-                                                           out.data_ptr(), out.stride(0), None,
-                                                           stats.data_ptr(), agg2.data_ptr(), s2.data_ptr(),
-                                                           int(drop[0]), float(drop[1]),
-                                                           graph.drop_ids("dst").data_ptr(), slab.data_ptr(), sb,
-                                                           _lib.MP_STAGE_ALL, st), "mp_gat_aggregate_train_drop_f32")
+            nat.mp_gat_aggregate_train_drop_f32(g, xw.data_ptr(), a_src.data_ptr(), a_dst.data_ptr(), att_c.data_ptr(),
+                                                H, C, float(slope), _lib.ptr(bias), out.data_ptr(), out.stride(0), None,
+                                                stats.data_ptr(), agg2.data_ptr(), s2.data_ptr(), int(drop[0]),
+                                                float(drop[1]), graph.drop_ids("dst").data_ptr(), slab.data_ptr(), sb,
+                                                _lib.MP_STAGE_ALL, st)
         else:
-            _lib.check(lib.mp_gat_aggregate_train_f32(g, xw.data_ptr(), a_src.data_ptr(), a_dst.data_ptr(),
-                                                      att_c.data_ptr(), H, C, float(slope), _lib.ptr(bias),
-                                                      out.data_ptr(), out.stride(0), None, stats.data_ptr(),
-                                                      agg2.data_ptr(), s2.data_ptr(), slab.data_ptr(), sb,
-                                                      _lib.MP_STAGE_ALL, st), "mp_gat_aggregate_train_f32")
+            nat.mp_gat_aggregate_train_f32(g, xw.data_ptr(), a_src.data_ptr(), a_dst.data_ptr(), att_c.data_ptr(), H, C,
+                                           float(slope), _lib.ptr(bias), out.data_ptr(), out.stride(0), None,
+                                           stats.data_ptr(), agg2.data_ptr(), s2.data_ptr(), slab.data_ptr(), sb,
+                                           _lib.MP_STAGE_ALL, st)
         extra = (agg2, s2)
     if extra is None:
-        sb = lib.mp_gat_slab_bytes(g, H, C)
+        sb = nat.mp_gat_slab_bytes(g, H, C)
         slab = torch.empty(sb, dtype=torch.uint8, device=dev)
         if nd:
-            _lib.check(lib.mp_gat_forward_f32(g, xw.data_ptr(), att_c.data_ptr(), H, C, float(slope), _lib.ptr(bias),
-                                              out.data_ptr(), out.stride(0), a_src.data_ptr(), a_dst.data_ptr(),
-                                              stats.data_ptr(), slab.data_ptr(), sb, _lib.MP_STAGE_ALL, st),
-                       "mp_gat_forward_f32")
+            nat.mp_gat_forward_f32(g, xw.data_ptr(), att_c.data_ptr(), H, C, float(slope), _lib.ptr(bias),
+                                   out.data_ptr(), out.stride(0), a_src.data_ptr(), a_dst.data_ptr(), stats.data_ptr(),
+                                   slab.data_ptr(), sb, _lib.MP_STAGE_ALL, st)
         elif gat_two_pass(csr, H, C):
-            _lib.check(lib.mp_gat_softmax_aggregate_f32(g, csr.slot_rows().data_ptr(), xw.data_ptr(), a_src.data_ptr(),
-                                                        a_dst.data_ptr(), H, C, float(slope), _lib.ptr(bias),
-                                                        out.data_ptr(), out.stride(0), stats.data_ptr(), slab.data_ptr(),
-                                                        sb, _lib.MP_STAGE_ALL, st), "mp_gat_softmax_aggregate_f32")
+            nat.mp_gat_softmax_aggregate_f32(g, csr.slot_rows().data_ptr(), xw.data_ptr(), a_src.data_ptr(),
+                                             a_dst.data_ptr(), H, C, float(slope), _lib.ptr(bias), out.data_ptr(),
+                                             out.stride(0), stats.data_ptr(), slab.data_ptr(), sb, _lib.MP_STAGE_ALL,
+                                             st)
         else:
-            _lib.check(lib.mp_gat_aggregate_att_f32(g, xw.data_ptr(), a_src.data_ptr(), a_dst.data_ptr(),
-                                                    att_c.data_ptr() if GAT_OWN_A_SRC else None, H, C, float(slope),
-                                                    _lib.ptr(bias), out.data_ptr(), out.stride(0), stats.data_ptr(),
-                                                    slab.data_ptr(), sb, _lib.MP_STAGE_ALL, st),
-                       "mp_gat_aggregate_att_f32")
+            nat.mp_gat_aggregate_att_f32(g, xw.data_ptr(), a_src.data_ptr(), a_dst.data_ptr(),
+                                         att_c.data_ptr() if GAT_OWN_A_SRC else None, H, C, float(slope),
+                                         _lib.ptr(bias), out.data_ptr(), out.stride(0), stats.data_ptr(),
+                                         slab.data_ptr(), sb, _lib.MP_STAGE_ALL, st)
     alpha = None
     if want_alpha:
         E = edge_index.shape[1]
         alpha = torch.empty((E, H), dtype=torch.float32, device=dev)
         src = edge_index[graph.j].contiguous()
         dst = edge_index[graph.i].contiguous()
-        _lib.check(lib.mp_gat_alpha_f32(src.data_ptr(), dst.data_ptr(), E, H, a_src.data_ptr(),
-                                        a_dst.data_ptr(), float(slope), stats.data_ptr(), alpha.data_ptr(), st),
-                   "mp_gat_alpha_f32")
+        nat.mp_gat_alpha_f32(src.data_ptr(), dst.data_ptr(), E, H, a_src.data_ptr(), a_dst.data_ptr(), float(slope),
+                             stats.data_ptr(), alpha.data_ptr(), st)
     return out, alpha, a_src, a_dst, stats, extra
 
 
 def _heads_aggregate(csr, gather, w_slot, H, x):
     """out[r, h*C+c] = sum_k w_slot[k, h] * x[col_k, h*C+c] (mp_aggregate_heads_f32)."""
-    lib = _lib.load()
+    nat = _lib.native()
     F = x.shape[1]
     out = torch.empty((csr.n_rows, F), dtype=torch.float32, device=x.device)
     if csr.n_rows == 0:
         return out
     g = csr.struct(gather)
-    sb = lib.mp_aggregate_slab_bytes(g, F, 0)
+    sb = nat.mp_aggregate_slab_bytes(g, F, 0)
     slab = torch.empty(sb, dtype=torch.uint8, device=x.device)
-    _lib.check(lib.mp_aggregate_heads_f32(g, w_slot.data_ptr(), H, x.data_ptr(), x.stride(0), F, out.data_ptr(),
-                                          out.stride(0), slab.data_ptr(), sb, _lib.MP_STAGE_ALL,
-                                          _lib.stream_ptr(x.device)), "mp_aggregate_heads_f32")
+    nat.mp_aggregate_heads_f32(g, w_slot.data_ptr(), H, x.data_ptr(), x.stride(0), F, out.data_ptr(), out.stride(0),
+                               slab.data_ptr(), sb, _lib.MP_STAGE_ALL, _lib.stream_ptr(x.device))
     return out
 
 
@@ -883,7 +856,7 @@ def _gat_backward_wide(graph, g, xw, att, a_src, a_dst, stats, agg, agg_bias, ex
     epilogue (d a_src = <acc2, xw> - sc, the att terms of d xw).  agg: the
     forward's output, agg_bias the bias inside it (None: none).
     Returns (d xw, d att or None, d bias or None)."""
-    lib = _lib.load()
+    nat = _lib.native()
     dev = xw.device
     st = _lib.stream_ptr(dev)
     N = xw.shape[0]
@@ -897,29 +870,24 @@ def _gat_backward_wide(graph, g, xw, att, a_src, a_dst, stats, agg, agg_bias, ex
     pack = torch.empty((max(n_dst, 1), H, 4), dtype=torch.float32, device=dev)
     ga_dst = (torch.empty if n_dst == N else torch.zeros)((N, H), dtype=torch.float32, device=dev)
     if n_dst:
-        _lib.check(lib.mp_gat_backward_prep_wide_f32(g.data_ptr(), g.stride(0), agg.data_ptr(), agg.stride(0),
-                                                     _lib.ptr(agg_bias), agg2.data_ptr(), s2.data_ptr(),
-                                                     a_dst.data_ptr(), stats.data_ptr(), n_dst, H, C, pack.data_ptr(),
-                                                     _lib.nbytes(pack), ga_dst.data_ptr(), st),
-                   "mp_gat_backward_prep_wide_f32")
+        nat.mp_gat_backward_prep_wide_f32(g.data_ptr(), g.stride(0), agg.data_ptr(), agg.stride(0), _lib.ptr(agg_bias),
+                                          agg2.data_ptr(), s2.data_ptr(), a_dst.data_ptr(), stats.data_ptr(), n_dst, H,
+                                          C, pack.data_ptr(), _lib.nbytes(pack), ga_dst.data_ptr(), st)
     src = graph.src_with_dst_slots()
     gs = src.struct("dst_slot")
     gx = torch.empty((N, F), dtype=torch.float32, device=dev)
     acc2 = torch.empty((N, F), dtype=torch.float32, device=dev)
     sc = torch.empty((N, H), dtype=torch.float32, device=dev)
-    sb = lib.mp_gat_train_slab_bytes(gs, H, C)
+    sb = nat.mp_gat_train_slab_bytes(gs, H, C)
     slab = torch.empty(sb, dtype=torch.uint8, device=dev)
     seed, p = (0, 0.0) if drop is None else (int(drop[0]), float(drop[1]))
     ids = graph.drop_ids("src").data_ptr() if drop is not None else None
-    _lib.check(lib.mp_gat_backward_wide_f32(gs, g.data_ptr(), g.stride(0), a_src.data_ptr(), pack.data_ptr(), H, C,
-                                            float(slope), seed, p, ids, gx.data_ptr(), acc2.data_ptr(),
-                                            _lib.nbytes(acc2),
-                                            sc.data_ptr(), _lib.nbytes(sc), slab.data_ptr(), sb, _lib.MP_STAGE_ALL, st),
-               "mp_gat_backward_wide_f32")
+    nat.mp_gat_backward_wide_f32(gs, g.data_ptr(), g.stride(0), a_src.data_ptr(), pack.data_ptr(), H, C, float(slope),
+                                 seed, p, ids, gx.data_ptr(), acc2.data_ptr(), _lib.nbytes(acc2), sc.data_ptr(),
+                                 _lib.nbytes(sc), slab.data_ptr(), sb, _lib.MP_STAGE_ALL, st)
     del slab, pack
-    _lib.check(lib.mp_gat_backward_epilogue_wide_f32(gx.data_ptr(), acc2.data_ptr(), xw.data_ptr(), att_c.data_ptr(),
-                                                     ga_dst.data_ptr(), sc.data_ptr(), N, H, C, st),
-               "mp_gat_backward_epilogue_wide_f32")
+    nat.mp_gat_backward_epilogue_wide_f32(gx.data_ptr(), acc2.data_ptr(), xw.data_ptr(), att_c.data_ptr(),
+                                          ga_dst.data_ptr(), sc.data_ptr(), N, H, C, st)
     del acc2
     ga_src = sc
     gatt = None
@@ -937,7 +905,7 @@ def _att_part_blocks(n_rows, n_dst):
     n_dst of them own), one partial per block of mp_gat_bwd_blocks(n_rows).
     (Round 4 sized this for n_dst: the library now rejects such a buffer --
     ABI 6 extents -- instead of writing past it; tests/test_gpu_dist.py.)"""
-    return int(_lib.load().mp_gat_bwd_blocks(n_rows))
+    return int(_lib.native().mp_gat_bwd_blocks(n_rows))
 
 
 def _gat_backward_fused(graph, g, xw, att, a_src, a_dst, stats, agg, agg_bias, H, C, slope, want_att, want_bias,
@@ -948,7 +916,7 @@ def _gat_backward_fused(graph, g, xw, att, a_src, a_dst, stats, agg, agg_bias, H
     src-slot map), and the epilogue (att_dst term + att-grad partials).  agg:
     the forward's output, agg_bias the bias inside it (None: none).
     Returns (d xw, d att or None, d bias or None)."""
-    lib = _lib.load()
+    nat = _lib.native()
     dev = xw.device
     st = _lib.stream_ptr(dev)
     N = xw.shape[0]
@@ -959,7 +927,7 @@ def _gat_backward_fused(graph, g, xw, att, a_src, a_dst, stats, agg, agg_bias, H
                 g.new_zeros(F) if want_bias else None)
     epi = C % 4 == 0 and F <= 256
     n_dst = graph.n_dst            # < N on a sharded rank's local graph (halo rows receive no edges)
-    nb = int(lib.mp_gat_bwd_blocks(n_dst))
+    nb = int(nat.mp_gat_bwd_blocks(n_dst))
     pack = torch.empty((max(n_dst, 1), H, 4), dtype=torch.float32, device=dev)
     gpart = torch.empty((nb, F), dtype=torch.float32, device=dev) if (want_bias and epi and n_dst) else None
     ga_dst = None
@@ -968,19 +936,14 @@ def _gat_backward_fused(graph, g, xw, att, a_src, a_dst, stats, agg, agg_bias, H
         agg2, s2 = extra
         ga_dst = (torch.empty if n_dst == N else torch.zeros)((N, H), dtype=torch.float32, device=dev)
         if n_dst:
-            _lib.check(lib.mp_gat_backward_prep_train_f32(g.data_ptr(), g.stride(0), agg.data_ptr(), agg.stride(0),
-                                                          _lib.ptr(agg_bias), agg2.data_ptr(), s2.data_ptr(),
-                                                          a_dst.data_ptr(), stats.data_ptr(), n_dst, H, C,
-                                                          pack.data_ptr(),
-                                                          _lib.nbytes(pack), _lib.ptr(gpart), _lib.nbytes(gpart),
-                                                          ga_dst.data_ptr(), st),
-                       "mp_gat_backward_prep_train_f32")
+            nat.mp_gat_backward_prep_train_f32(g.data_ptr(), g.stride(0), agg.data_ptr(), agg.stride(0),
+                                               _lib.ptr(agg_bias), agg2.data_ptr(), s2.data_ptr(), a_dst.data_ptr(),
+                                               stats.data_ptr(), n_dst, H, C, pack.data_ptr(), _lib.nbytes(pack),
+                                               _lib.ptr(gpart), _lib.nbytes(gpart), ga_dst.data_ptr(), st)
     elif n_dst:
-        _lib.check(lib.mp_gat_backward_prep_f32(g.data_ptr(), g.stride(0), agg.data_ptr(), agg.stride(0),
-                                                _lib.ptr(agg_bias), a_dst.data_ptr(), stats.data_ptr(), n_dst, H, C,
-                                                pack.data_ptr(), _lib.nbytes(pack), _lib.ptr(gpart), _lib.nbytes(gpart),
-                                                st),
-                   "mp_gat_backward_prep_f32")
+        nat.mp_gat_backward_prep_f32(g.data_ptr(), g.stride(0), agg.data_ptr(), agg.stride(0), _lib.ptr(agg_bias),
+                                     a_dst.data_ptr(), stats.data_ptr(), n_dst, H, C, pack.data_ptr(),
+                                     _lib.nbytes(pack), _lib.ptr(gpart), _lib.nbytes(gpart), st)
     gb = None
     if want_bias:
         gb = gpart.sum(0) if gpart is not None else g.sum(0)
@@ -991,29 +954,25 @@ def _gat_backward_fused(graph, g, xw, att, a_src, a_dst, stats, agg, agg_bias, H
     # per-edge d score in dst-CSR slot order (only without the training forward's extras)
     de = torch.empty((max(E, 1), H), dtype=torch.float32, device=dev) if ga_dst is None else None
     gs = src.struct("dst_slot")
-    sb = lib.mp_gat_slab_bytes(gs, H, C)
+    sb = nat.mp_gat_slab_bytes(gs, H, C)
     slab = torch.empty(sb, dtype=torch.uint8, device=dev)
     fused_dst = ga_dst is not None
     if drop is not None:
         if not fused_dst:
             raise ValueError("mi355_mp: the attention-dropout backward needs the training forward's extras")
-        _lib.check(lib.mp_gat_backward_train_drop_f32(gs, g.data_ptr(), g.stride(0), xw.data_ptr(), a_src.data_ptr(),
-                                                      pack.data_ptr(), att_c.data_ptr(), H, C, float(slope),
-                                                      ga_dst.data_ptr(), int(drop[0]), float(drop[1]),
-                                                      graph.drop_ids("src").data_ptr(), gx.data_ptr(),
-                                                      ga_src.data_ptr(), slab.data_ptr(), sb, _lib.MP_STAGE_ALL, st),
-                   "mp_gat_backward_train_drop_f32")
+        nat.mp_gat_backward_train_drop_f32(gs, g.data_ptr(), g.stride(0), xw.data_ptr(), a_src.data_ptr(),
+                                           pack.data_ptr(), att_c.data_ptr(), H, C, float(slope), ga_dst.data_ptr(),
+                                           int(drop[0]), float(drop[1]), graph.drop_ids("src").data_ptr(),
+                                           gx.data_ptr(), ga_src.data_ptr(), slab.data_ptr(), sb, _lib.MP_STAGE_ALL, st)
     elif fused_dst:
         # the transposed pass also adds d a_dst (x) att_dst to each row's d xw
-        _lib.check(lib.mp_gat_backward_train_f32(gs, g.data_ptr(), g.stride(0), xw.data_ptr(), a_src.data_ptr(),
-                                                 pack.data_ptr(), att_c.data_ptr(), H, C, float(slope),
-                                                 ga_dst.data_ptr(), gx.data_ptr(), ga_src.data_ptr(), slab.data_ptr(),
-                                                 sb, _lib.MP_STAGE_ALL, st), "mp_gat_backward_train_f32")
+        nat.mp_gat_backward_train_f32(gs, g.data_ptr(), g.stride(0), xw.data_ptr(), a_src.data_ptr(), pack.data_ptr(),
+                                      att_c.data_ptr(), H, C, float(slope), ga_dst.data_ptr(), gx.data_ptr(),
+                                      ga_src.data_ptr(), slab.data_ptr(), sb, _lib.MP_STAGE_ALL, st)
     else:
-        _lib.check(lib.mp_gat_backward_f32(gs, g.data_ptr(), g.stride(0), xw.data_ptr(), a_src.data_ptr(),
-                                           pack.data_ptr(), att_c.data_ptr(), H, C, float(slope), gx.data_ptr(),
-                                           ga_src.data_ptr(), _lib.ptr(de), _lib.nbytes(de), slab.data_ptr(), sb,
-                                           _lib.MP_STAGE_ALL, st), "mp_gat_backward_f32")
+        nat.mp_gat_backward_f32(gs, g.data_ptr(), g.stride(0), xw.data_ptr(), a_src.data_ptr(), pack.data_ptr(),
+                                att_c.data_ptr(), H, C, float(slope), gx.data_ptr(), ga_src.data_ptr(), _lib.ptr(de),
+                                _lib.nbytes(de), slab.data_ptr(), sb, _lib.MP_STAGE_ALL, st)
     del slab, pack
     if ga_dst is None:
         ga_dst, _ = _aggregate(graph.dst, "slot", de, None, "sum", 0, None)
@@ -1026,17 +985,16 @@ def _gat_backward_fused(graph, g, xw, att, a_src, a_dst, stats, agg, agg_bias, H
             # the finish pass runs over all N rows (own + halo on a sharded rank's
             # local graph), one partial per block of mp_gat_bwd_blocks(N)
             apart = torch.empty((_att_part_blocks(N, n_dst), 2, F), dtype=torch.float32, device=dev)
-            _lib.check(lib.mp_gat_backward_finish_f32(None if fused_dst else gx.data_ptr(), xw.data_ptr(),
-                                                      ga_dst.data_ptr(), ga_src.data_ptr(), att_c.data_ptr(), N, H, C,
-                                                      apart.data_ptr(), _lib.nbytes(apart), st),
-                       "mp_gat_backward_finish_f32")
+            nat.mp_gat_backward_finish_f32(None if fused_dst else gx.data_ptr(), xw.data_ptr(), ga_dst.data_ptr(),
+                                           ga_src.data_ptr(), att_c.data_ptr(), N, H, C, apart.data_ptr(),
+                                           _lib.nbytes(apart), st)
         if want_att:
             p = apart.sum(0).view(2, H, C)
             gatt = torch.cat([p[0], p[1]], dim=-1).view_as(att)
     else:
         if not fused_dst:
-            _lib.check(lib.mp_heads_outer_add_f32(gx.data_ptr(), gx.stride(0), ga_dst.data_ptr(), N, H, C,
-                                                  att_c.data_ptr(), 2 * C, st), "mp_heads_outer_add_f32")
+            nat.mp_heads_outer_add_f32(gx.data_ptr(), gx.stride(0), ga_dst.data_ptr(), N, H, C, att_c.data_ptr(), 2 * C,
+                                       st)
         if want_att:
             x3 = xw.view(N, H, C)
             gatt = torch.cat([torch.einsum("nh,nhc->hc", ga_dst, x3), torch.einsum("nh,nhc->hc", ga_src, x3)],
@@ -1083,7 +1041,7 @@ class _GatPropagate(torch.autograd.Function):
           de     = ds * leaky'(s);  d a_dst = row sums, d a_src = column sums of de
           dxw   += d a_src (x) att_src + d a_dst (x) att_dst;  d att = sum_n d a (x) xw
         Only [E, H]-sized arrays are materialised, never [E, H*C]."""
-        lib = _lib.load()
+        nat = _lib.native()
         xw, att, edge_index, a_src, a_dst, stats, agg, agg_bias = ctx.saved_tensors[:8]
         extra = tuple(ctx.saved_tensors[8:10]) if ctx.has_extra else None
         graph, H, C, slope = ctx.graph, ctx.H, ctx.C, ctx.slope
@@ -1109,9 +1067,8 @@ class _GatPropagate(torch.autograd.Function):
         sr = dst.slot_rows()
         alpha = torch.empty((max(E, 1), H), dtype=torch.float32, device=dev)
         score = torch.empty_like(alpha)
-        _lib.check(lib.mp_gat_alpha_csr_f32(dst.struct("other"), sr.data_ptr(), a_src.data_ptr(), a_dst.data_ptr(),
-                                            H, float(slope), stats.data_ptr(), alpha.data_ptr(), score.data_ptr(),
-                                            st), "mp_gat_alpha_csr_f32")
+        nat.mp_gat_alpha_csr_f32(dst.struct("other"), sr.data_ptr(), a_src.data_ptr(), a_dst.data_ptr(), H,
+                                 float(slope), stats.data_ptr(), alpha.data_ptr(), score.data_ptr(), st)
         eid_d = dst.eid[:E].long()
         # message part of d xw: alpha in the transposed CSR's slot order
         alpha_orig = torch.empty_like(alpha)
@@ -1120,8 +1077,8 @@ class _GatPropagate(torch.autograd.Function):
         gx = _heads_aggregate(src, "other", alpha_src, H, g)
         # d alpha (CSR order) and the softmax backward
         dalpha = torch.empty_like(alpha)
-        _lib.check(lib.mp_gat_sddmm_f32(dst.struct("other"), sr.data_ptr(), g.data_ptr(), g.stride(0), xw.data_ptr(),
-                                        xw.stride(0), H, C, dalpha.data_ptr(), st), "mp_gat_sddmm_f32")
+        nat.mp_gat_sddmm_f32(dst.struct("other"), sr.data_ptr(), g.data_ptr(), g.stride(0), xw.data_ptr(), xw.stride(0),
+                             H, C, dalpha.data_ptr(), st)
         t = (alpha * dalpha)[:E].contiguous()
         rs, _ = _aggregate(dst, "slot", t, None, "sum", 0, None)             # sum over each row's slots
         ds = alpha[:E] * (dalpha[:E] - rs[sr[:E].long()])
@@ -1254,7 +1211,7 @@ def gemm_rows(x, w, force_generic=False):
     """x @ w (fp32, device) with every output row the k-ordered fmaf chain of
     its own input row (mp_gemm_rows_f32): bitwise independent of how many rows
     x has -- a shard's rows equal the single-GPU rows.  No autograd."""
-    lib = _lib.load()
+    nat = _lib.native()
     _lib.require_device(x)
     if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[0]:
         raise ValueError("gemm_rows: x [M, K] and w [K, N] (got %s and %s)" % (tuple(x.shape), tuple(w.shape)))
@@ -1267,8 +1224,8 @@ def gemm_rows(x, w, force_generic=False):
     N = w.shape[1]
     out = torch.empty((M, N), dtype=torch.float32, device=x.device)
     if M and K and N:
-        _lib.check(lib.mp_gemm_rows_f32(x.data_ptr(), x.stride(0), M, K, w.data_ptr(), 0, N, out.data_ptr(), N,
-                                        int(bool(force_generic)), _lib.stream_ptr(x.device)), "mp_gemm_rows_f32")
+        nat.mp_gemm_rows_f32(x.data_ptr(), x.stride(0), M, K, w.data_ptr(), 0, N, out.data_ptr(), N,
+                             int(bool(force_generic)), _lib.stream_ptr(x.device))
     elif M and N:
         out.zero_()
     return out
@@ -1328,10 +1285,10 @@ def _spline_geom(kernel_size, is_open_spline, degree, D, F=1):
                          % (D, len(ks), len(op)))
     ks_a = (_lib.i32 * max(D, 1))(*ks)
     op_a = (_lib.i32 * max(D, 1))(*op)
-    lib = _lib.load()
-    if not lib.mp_spline_ok(D, degree, ks_a, op_a, max(int(F), 1)):
+    nat = _lib.native()
+    if not nat.mp_spline_ok(D, degree, ks_a, op_a, max(int(F), 1)):
         raise NotImplementedError("mi355_mp: outside the fused spline path's limits: "
-                                  + lib.mp_last_error().decode(errors="replace"))
+                                  + nat.mp_last_error().decode(errors="replace"))
     K = 1
     for k in ks:
         K *= k
@@ -1357,9 +1314,9 @@ def spline_basis(pseudo, kernel_size, is_open_spline, degree):
     ks_a, op_a, _K, S = _spline_geom(kernel_size, is_open_spline, degree, D)
     basis = torch.empty((E, S), dtype=torch.float32, device=pseudo.device)
     wi = torch.empty((E, S), dtype=torch.int64, device=pseudo.device)
-    _lib.check(_lib.load().mp_spline_basis_f32(pseudo.data_ptr(), E, D, ks_a, op_a, int(degree), basis.data_ptr(),
-                                               _lib.nbytes(basis), wi.data_ptr(), _lib.nbytes(wi),
-                                               _lib.stream_ptr(pseudo.device)), "mp_spline_basis_f32")
+    _lib.native().mp_spline_basis_f32(pseudo.data_ptr(), E, D, ks_a, op_a, int(degree), basis.data_ptr(),
+                                      _lib.nbytes(basis), wi.data_ptr(), _lib.nbytes(wi),
+                                      _lib.stream_ptr(pseudo.device))
     return basis, wi
 
 
@@ -1371,10 +1328,10 @@ def spline_bins(csr, pseudo, geom, degree, x, row_scale=None):
     F = x.shape[1]
     out = torch.empty((csr.n_rows, K * F), dtype=torch.float32, device=x.device)
     if csr.n_rows and F:
-        _lib.check(_lib.load().mp_spline_aggregate_bins_f32(
-            csr.struct("other"), pseudo.data_ptr(), pseudo.shape[0], pseudo.shape[1], ks_a, op_a, int(degree),
-            x.data_ptr(), x.stride(0), F, _lib.ptr(row_scale), out.data_ptr(), out.stride(0),
-            _lib.stream_ptr(x.device)), "mp_spline_aggregate_bins_f32")
+        _lib.native().mp_spline_aggregate_bins_f32(csr.struct("other"), pseudo.data_ptr(), pseudo.shape[0],
+                                                   pseudo.shape[1], ks_a, op_a, int(degree), x.data_ptr(), x.stride(0),
+                                                   F, _lib.ptr(row_scale), out.data_ptr(), out.stride(0),
+                                                   _lib.stream_ptr(x.device))
     return out
 
 
@@ -1385,10 +1342,10 @@ def spline_gather(csr, pseudo, geom, degree, xk, F, row_scale=None, bias=None):
     ks_a, op_a, K, _S = geom
     out = torch.empty((csr.n_rows, F), dtype=torch.float32, device=xk.device)
     if csr.n_rows and F:
-        _lib.check(_lib.load().mp_spline_aggregate_gather_f32(
-            csr.struct("other"), pseudo.data_ptr(), pseudo.shape[0], pseudo.shape[1], ks_a, op_a, int(degree),
-            xk.data_ptr(), xk.stride(0), F, _lib.ptr(row_scale), _lib.ptr(bias), out.data_ptr(), out.stride(0),
-            _lib.stream_ptr(xk.device)), "mp_spline_aggregate_gather_f32")
+        _lib.native().mp_spline_aggregate_gather_f32(csr.struct("other"), pseudo.data_ptr(), pseudo.shape[0],
+                                                     pseudo.shape[1], ks_a, op_a, int(degree), xk.data_ptr(),
+                                                     xk.stride(0), F, _lib.ptr(row_scale), _lib.ptr(bias),
+                                                     out.data_ptr(), out.stride(0), _lib.stream_ptr(xk.device))
     return out
 
 
@@ -1534,14 +1491,14 @@ def check_ratio(ratio):
 def topk_path(n_g):
     """0 = one wave, 1 = one workgroup, 2 = sorted: how mp_topk_select_f32 ranks a
     graph of n_g nodes (mp_topk_path; needs no GPU)."""
-    return int(_lib.load().mp_topk_path(int(n_g)))
+    return int(_lib.native().mp_topk_path(int(n_g)))
 
 
 def batch_layout(batch, n, device=None):
     """BatchLayout of `batch` ([n] int64 on the device, or None = one graph).
     One host read (graphs, largest graph and sortedness together); none for
     batch None."""
-    lib = _lib.load()
+    nat = _lib.native()
     n = int(n)
     if batch is None:
         starts = torch.tensor([0, n], dtype=torch.int64).to(device)
@@ -1553,11 +1510,10 @@ def batch_layout(batch, n, device=None):
     dev = batch.device
     st = _lib.stream_ptr(dev)
     stats = torch.empty(3, dtype=torch.int64, device=dev)
-    _lib.check(lib.mp_batch_stats(batch.data_ptr(), n, stats.data_ptr(), _lib.nbytes(stats), st), "mp_batch_stats")
+    nat.mp_batch_stats(batch.data_ptr(), n, stats.data_ptr(), _lib.nbytes(stats), st)
     G, max_n, unsorted = stats.tolist()
     starts = torch.empty(G + 1, dtype=torch.int64, device=dev)
-    _lib.check(lib.mp_batch_starts(batch.data_ptr(), n, G, starts.data_ptr(), _lib.nbytes(starts), st),
-               "mp_batch_starts")
+    nat.mp_batch_starts(batch.data_ptr(), n, G, starts.data_ptr(), _lib.nbytes(starts), st)
     return BatchLayout(starts, G, min(max_n, n), unsorted, n)
 
 
@@ -1576,7 +1532,7 @@ class _PoolScore(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, attn, weight, flags):
-        lib = _lib.load()
+        nat = _lib.native()
         attn = _pool_rows(attn, "attn")
         w = weight.detach().reshape(-1).contiguous()
         n, F = attn.shape
@@ -1584,8 +1540,8 @@ class _PoolScore(torch.autograd.Function):
             raise ValueError("mi355_mp: weight must be float32 with %d entries (got %s %s)"
                              % (F, weight.dtype, tuple(weight.shape)))
         score = torch.empty(n, dtype=torch.float32, device=attn.device)
-        _lib.check(lib.mp_pool_score_f32(attn.data_ptr(), attn.stride(0), n, F, w.data_ptr(), flags, score.data_ptr(),
-                                         _lib.nbytes(score), _lib.stream_ptr(attn.device)), "mp_pool_score_f32")
+        nat.mp_pool_score_f32(attn.data_ptr(), attn.stride(0), n, F, w.data_ptr(), flags, score.data_ptr(),
+                              _lib.nbytes(score), _lib.stream_ptr(attn.device))
         ctx.flags = flags
         ctx.wshape = weight.shape
         ctx.save_for_backward(attn, w, score)
@@ -1593,19 +1549,18 @@ class _PoolScore(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        lib = _lib.load()
+        nat = _lib.native()
         attn, w, score = ctx.saved_tensors
         n, F = attn.shape
         dev = attn.device
         g = g.contiguous()
         g_attn = torch.empty((n, F), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
         g_w = torch.empty(F, dtype=torch.float32, device=dev)
-        wsb = lib.mp_pool_score_bwd_workspace(n, F)
+        wsb = nat.mp_pool_score_bwd_workspace(n, F)
         ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-        _lib.check(lib.mp_pool_score_bwd_f32(attn.data_ptr(), attn.stride(0), n, F, w.data_ptr(), ctx.flags,
-                                             score.data_ptr(), g.data_ptr(), _lib.ptr(g_attn), F, g_w.data_ptr(),
-                                             _lib.nbytes(g_w), ws.data_ptr(), wsb, _lib.stream_ptr(dev)),
-                   "mp_pool_score_bwd_f32")
+        nat.mp_pool_score_bwd_f32(attn.data_ptr(), attn.stride(0), n, F, w.data_ptr(), ctx.flags, score.data_ptr(),
+                                  g.data_ptr(), _lib.ptr(g_attn), F, g_w.data_ptr(), _lib.nbytes(g_w), ws.data_ptr(),
+                                  wsb, _lib.stream_ptr(dev))
         return g_attn, (g_w.view(ctx.wshape) if ctx.needs_input_grad[1] else None), None
 
 
@@ -1625,10 +1580,9 @@ def topk_counts(starts, ratio, max_n=None):
     G = starts.numel() - 1
     out_starts = torch.empty(G + 1, dtype=torch.int64, device=starts.device)
     counts = torch.zeros(4, dtype=torch.int64, device=starts.device)
-    _lib.check(_lib.load().mp_topk_counts(starts.data_ptr(), G, check_ratio(ratio),
-                                          (1 << 62) if max_n is None else int(max_n), out_starts.data_ptr(),
-                                          _lib.nbytes(out_starts), counts.data_ptr(),
-                                          _lib.stream_ptr(starts.device)), "mp_topk_counts")
+    _lib.native().mp_topk_counts(starts.data_ptr(), G, check_ratio(ratio), (1 << 62) if max_n is None else int(max_n),
+                                 out_starts.data_ptr(), _lib.nbytes(out_starts), counts.data_ptr(),
+                                 _lib.stream_ptr(starts.device))
     return out_starts, counts
 
 
@@ -1647,7 +1601,7 @@ def topk_select(score, ratio, layout):
     of every graph by descending score, equal scores by ascending index.  No
     host read: K stays in counts[0]."""
     _lib.require_device(score)
-    lib = _lib.load()
+    nat = _lib.native()
     ratio = check_ratio(ratio)
     score = score.detach()
     if score.dtype != torch.float32 or score.dim() != 1 or score.shape[0] != layout.n:
@@ -1659,12 +1613,11 @@ def topk_select(score, ratio, layout):
     inv = torch.empty(n, dtype=torch.int64, device=dev)
     out_starts = torch.empty(G + 1, dtype=torch.int64, device=dev)
     counts = torch.zeros(4, dtype=torch.int64, device=dev)
-    wsb = lib.mp_topk_workspace(n, G, layout.max_n)
+    wsb = nat.mp_topk_workspace(n, G, layout.max_n)
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    _lib.check(lib.mp_topk_select_f32(score.data_ptr(), n, layout.starts.data_ptr(), G, layout.max_n, ratio,
-                                      perm.data_ptr(), _lib.nbytes(perm), out_starts.data_ptr(),
-                                      _lib.nbytes(out_starts), inv.data_ptr(), _lib.nbytes(inv), counts.data_ptr(),
-                                      ws.data_ptr(), wsb, _lib.stream_ptr(dev)), "mp_topk_select_f32")
+    nat.mp_topk_select_f32(score.data_ptr(), n, layout.starts.data_ptr(), G, layout.max_n, ratio, perm.data_ptr(),
+                           _lib.nbytes(perm), out_starts.data_ptr(), _lib.nbytes(out_starts), inv.data_ptr(),
+                           _lib.nbytes(inv), counts.data_ptr(), ws.data_ptr(), wsb, _lib.stream_ptr(dev))
     return PoolSelection(perm, out_starts, inv, counts)
 
 
@@ -1672,17 +1625,17 @@ def pool_compact(keep, counts=None):
     """(pos, counts): pos[:counts[0]] = the positions with keep != 0 in ascending
     order (mp_pool_compact; pos is sized n).  No host read."""
     _lib.require_device(keep)
-    lib = _lib.load()
+    nat = _lib.native()
     keep = keep.to(torch.uint8).contiguous()
     n = keep.numel()
     dev = keep.device
     pos = torch.empty(n, dtype=torch.int64, device=dev)
     if counts is None:
         counts = torch.zeros(4, dtype=torch.int64, device=dev)
-    wsb = lib.mp_pool_compact_workspace(n)
+    wsb = nat.mp_pool_compact_workspace(n)
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    _lib.check(lib.mp_pool_compact(keep.data_ptr(), n, pos.data_ptr(), _lib.nbytes(pos), counts.data_ptr(),
-                                   ws.data_ptr(), wsb, _lib.stream_ptr(dev)), "mp_pool_compact")
+    nat.mp_pool_compact(keep.data_ptr(), n, pos.data_ptr(), _lib.nbytes(pos), counts.data_ptr(), ws.data_ptr(), wsb,
+                        _lib.stream_ptr(dev))
     return pos, counts
 
 
@@ -1692,9 +1645,8 @@ def pool_inverse(perm, n, k_dev=None):
     _lib.require_device(perm)
     perm = perm.to(torch.int64).contiguous()
     inv = torch.empty(int(n), dtype=torch.int64, device=perm.device)
-    _lib.check(_lib.load().mp_pool_inverse(perm.data_ptr(), min(perm.numel(), int(n)), _lib.ptr(k_dev), int(n),
-                                           inv.data_ptr(), _lib.nbytes(inv), _lib.stream_ptr(perm.device)),
-               "mp_pool_inverse")
+    _lib.native().mp_pool_inverse(perm.data_ptr(), min(perm.numel(), int(n)), _lib.ptr(k_dev), int(n), inv.data_ptr(),
+                                  _lib.nbytes(inv), _lib.stream_ptr(perm.device))
     return inv
 
 
@@ -1720,19 +1672,18 @@ def pool_filter_adj(edge_index, sel, n):
     pos [E]) sized at their upper bound; sel.counts[1] = kept edges, [2] = edge
     ends outside [0, n).  No host read."""
     _lib.require_device(edge_index)
-    lib = _lib.load()
+    nat = _lib.native()
     dev = edge_index.device
     E = int(edge_index.shape[1])
     row = edge_index[0].to(torch.int64).contiguous()
     col = edge_index[1].to(torch.int64).contiguous()
     out = torch.empty((2, E), dtype=torch.int64, device=dev)
     pos = torch.empty(E, dtype=torch.int64, device=dev)
-    wsb = lib.mp_pool_filter_workspace(E)
+    wsb = nat.mp_pool_filter_workspace(E)
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    _lib.check(lib.mp_pool_filter_adj(row.data_ptr(), col.data_ptr(), E, sel.inv.data_ptr(), int(n),
-                                      out[0].data_ptr(), out[1].data_ptr(), pos.data_ptr(), E * 8,
-                                      sel.counts.data_ptr(), ws.data_ptr(), wsb, _lib.stream_ptr(dev)),
-               "mp_pool_filter_adj")
+    nat.mp_pool_filter_adj(row.data_ptr(), col.data_ptr(), E, sel.inv.data_ptr(), int(n), out[0].data_ptr(),
+                           out[1].data_ptr(), pos.data_ptr(), E * 8, sel.counts.data_ptr(), ws.data_ptr(), wsb,
+                           _lib.stream_ptr(dev))
     return out, pos
 
 
@@ -1754,7 +1705,7 @@ class _PoolGate(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, score, perm, inv, batch, multiplier):
-        lib = _lib.load()
+        nat = _lib.native()
         x = _pool_rows(x, "x")
         score = score.contiguous()
         n, F = x.shape
@@ -1763,10 +1714,9 @@ class _PoolGate(torch.autograd.Function):
         x_out = torch.empty((k, F), dtype=torch.float32, device=dev)
         score_out = torch.empty(k, dtype=torch.float32, device=dev)
         batch_out = torch.empty(k, dtype=torch.int64, device=dev)
-        _lib.check(lib.mp_pool_gate_f32(x.data_ptr(), x.stride(0), score.data_ptr(), _lib.ptr(batch), perm.data_ptr(),
-                                        k, n, F, float(multiplier), x_out.data_ptr(), F, _lib.nbytes(x_out),
-                                        batch_out.data_ptr(), score_out.data_ptr(), _lib.stream_ptr(dev)),
-                   "mp_pool_gate_f32")
+        nat.mp_pool_gate_f32(x.data_ptr(), x.stride(0), score.data_ptr(), _lib.ptr(batch), perm.data_ptr(), k, n, F,
+                             float(multiplier), x_out.data_ptr(), F, _lib.nbytes(x_out), batch_out.data_ptr(),
+                             score_out.data_ptr(), _lib.stream_ptr(dev))
         ctx.k, ctx.multiplier = k, float(multiplier)
         ctx.save_for_backward(x, score, inv)
         ctx.mark_non_differentiable(batch_out)
@@ -1774,7 +1724,7 @@ class _PoolGate(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_y, g_t, _g_b=None):
-        lib = _lib.load()
+        nat = _lib.native()
         x, score, inv = ctx.saved_tensors
         n, F = x.shape
         dev = x.device
@@ -1782,10 +1732,9 @@ class _PoolGate(torch.autograd.Function):
         g_t = g_t.contiguous()
         g_x = torch.empty((n, F), dtype=torch.float32, device=dev)
         g_s = torch.empty(n, dtype=torch.float32, device=dev)
-        _lib.check(lib.mp_pool_gate_bwd_f32(g_y.data_ptr(), F, g_t.data_ptr(), x.data_ptr(), x.stride(0),
-                                            score.data_ptr(), inv.data_ptr(), ctx.k, n, F, ctx.multiplier,
-                                            g_x.data_ptr(), F, _lib.nbytes(g_x), g_s.data_ptr(), _lib.nbytes(g_s),
-                                            _lib.stream_ptr(dev)), "mp_pool_gate_bwd_f32")
+        nat.mp_pool_gate_bwd_f32(g_y.data_ptr(), F, g_t.data_ptr(), x.data_ptr(), x.stride(0), score.data_ptr(),
+                                 inv.data_ptr(), ctx.k, n, F, ctx.multiplier, g_x.data_ptr(), F, _lib.nbytes(g_x),
+                                 g_s.data_ptr(), _lib.nbytes(g_s), _lib.stream_ptr(dev))
         return g_x, g_s, None, None, None, None
 
 
@@ -1831,9 +1780,8 @@ def _gather_rows_bytes(attr, pos):
     k, F = pos.numel(), flat.shape[1]
     out = torch.empty((k, F), dtype=attr.dtype, device=attr.device)
     if k and F:
-        _lib.check(_lib.load().mp_gather_rows_any(flat.element_size(), flat.data_ptr(), flat.stride(0), pos.data_ptr(),
-                                                  k, F, out.data_ptr(), F, _lib.stream_ptr(attr.device)),
-                   "mp_gather_rows_any")
+        _lib.native().mp_gather_rows_any(flat.element_size(), flat.data_ptr(), flat.stride(0), pos.data_ptr(), k, F,
+                                         out.data_ptr(), F, _lib.stream_ptr(attr.device))
     return out.view((k,) + tuple(attr.shape[1:]))
 
 
@@ -1917,9 +1865,9 @@ def voxel_keys(pos, batch, size, start, end):
             raise ValueError("mi355_mp: %s must be float32 [%d] (got %s %s)" % (name, Dt, t.dtype, tuple(t.shape)))
         geo.append(t.contiguous())
     key = torch.empty(n, dtype=torch.int64, device=pos.device)
-    _lib.check(_lib.load().mp_voxel_keys_f32(pos.data_ptr(), pos.stride(0), n, D, _lib.ptr(batch), geo[0].data_ptr(),
-                                             geo[1].data_ptr(), geo[2].data_ptr(), key.data_ptr(), _lib.nbytes(key),
-                                             _lib.stream_ptr(pos.device)), "mp_voxel_keys_f32")
+    _lib.native().mp_voxel_keys_f32(pos.data_ptr(), pos.stride(0), n, D, _lib.ptr(batch), geo[0].data_ptr(),
+                                    geo[1].data_ptr(), geo[2].data_ptr(), key.data_ptr(), _lib.nbytes(key),
+                                    _lib.stream_ptr(pos.device))
     return key
 
 
@@ -1945,7 +1893,7 @@ def cluster_build(key):
     _lib.require_device(key)
     if key.dtype != torch.int64 or key.dim() != 1:
         raise ValueError("mi355_mp: cluster must be a 1-D int64 tensor (got %s %s)" % (key.dtype, tuple(key.shape)))
-    lib = _lib.load()
+    nat = _lib.native()
     key = key.contiguous()
     n = key.numel()
     dev = key.device
@@ -1954,12 +1902,11 @@ def cluster_build(key):
     member = torch.empty(n, dtype=torch.int32, device=dev)
     perm = torch.empty(n, dtype=torch.int64, device=dev)
     counts = torch.zeros(4, dtype=torch.int64, device=dev)
-    wsb = lib.mp_cluster_build_workspace(n)
+    wsb = nat.mp_cluster_build_workspace(n)
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    _lib.check(lib.mp_cluster_build(key.data_ptr(), n, inv.data_ptr(), _lib.nbytes(inv), rowptr.data_ptr(),
-                                    _lib.nbytes(rowptr), member.data_ptr(), _lib.nbytes(member), perm.data_ptr(),
-                                    _lib.nbytes(perm), counts.data_ptr(), ws.data_ptr(), wsb, _lib.stream_ptr(dev)),
-               "mp_cluster_build")
+    nat.mp_cluster_build(key.data_ptr(), n, inv.data_ptr(), _lib.nbytes(inv), rowptr.data_ptr(), _lib.nbytes(rowptr),
+                         member.data_ptr(), _lib.nbytes(member), perm.data_ptr(), _lib.nbytes(perm), counts.data_ptr(),
+                         ws.data_ptr(), wsb, _lib.stream_ptr(dev))
     return ClusterSelection(inv, rowptr, member, perm, counts, n)
 
 
@@ -1983,7 +1930,7 @@ class _ClusterReduce(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, pos, sel, reduce, batch, pyg_mask):
-        lib = _lib.load()
+        nat = _lib.native()
         n = sel.n
         dev = sel.inv.device
         is_max = reduce == "max"
@@ -2004,12 +1951,12 @@ class _ClusterReduce(torch.autograd.Function):
             batch_out = torch.empty(n, dtype=torch.int64, device=dev)
         flags = _lib.MP_FLAG_PYG_MASK if (pyg_mask and is_max and not need_mask_grad) else 0
         if n:
-            _lib.check(lib.mp_cluster_reduce_f32(
-                _lib.ptr(x), x.stride(0) if F else 0, F, _lib.MP_REDUCE[reduce], flags, sel.rowptr.data_ptr(),
-                sel.member.data_ptr(), sel.counts.data_ptr(), n, _lib.ptr(x_out), F, _lib.nbytes(x_out),
-                _lib.ptr(arg), _lib.nbytes(arg), _lib.ptr(pos), pos.stride(0) if Dp else 0, Dp, _lib.ptr(pos_out),
-                _lib.nbytes(pos_out), _lib.ptr(batch), sel.perm.data_ptr(), _lib.ptr(batch_out),
-                _lib.nbytes(batch_out), _lib.stream_ptr(dev)), "mp_cluster_reduce_f32")
+            nat.mp_cluster_reduce_f32(_lib.ptr(x), x.stride(0) if F else 0, F, _lib.MP_REDUCE[reduce], flags,
+                                      sel.rowptr.data_ptr(), sel.member.data_ptr(), sel.counts.data_ptr(), n,
+                                      _lib.ptr(x_out), F, _lib.nbytes(x_out), _lib.ptr(arg), _lib.nbytes(arg),
+                                      _lib.ptr(pos), pos.stride(0) if Dp else 0, Dp, _lib.ptr(pos_out),
+                                      _lib.nbytes(pos_out), _lib.ptr(batch), sel.perm.data_ptr(), _lib.ptr(batch_out),
+                                      _lib.nbytes(batch_out), _lib.stream_ptr(dev))
         if need_mask_grad:
             keep = ~(x_out < -10000)
             x_out = x_out.masked_fill(~keep, 0.0)
@@ -2037,9 +1984,8 @@ class _ClusterReduce(torch.autograd.Function):
             g = g.contiguous()
             if ctx.is_max:
                 gx = torch.zeros((n, ctx.F), dtype=torch.float32, device=g.device)
-                _lib.check(_lib.load().mp_scatter_arg_backward_f32(g.data_ptr(), arg.data_ptr(), M, ctx.F, n,
-                                                                   gx.data_ptr(), ctx.F, _lib.stream_ptr(g.device)),
-                           "mp_scatter_arg_backward_f32")
+                _lib.native().mp_scatter_arg_backward_f32(g.data_ptr(), arg.data_ptr(), M, ctx.F, n, gx.data_ptr(),
+                                                          ctx.F, _lib.stream_ptr(g.device))
             else:
                 gx = gather_rows(g / cnt, sel.inv)
         if ctx.Dp and ctx.needs_input_grad[1] and g_pos is not None:
@@ -2083,7 +2029,7 @@ def pool_edges(edge_index, sel):
     the loops, sort the pairs and merge the duplicates; sel.counts[1] = output
     edges, [2] = edge ends outside [0, n).  No host read."""
     _lib.require_device(edge_index)
-    lib = _lib.load()
+    nat = _lib.native()
     dev = edge_index.device
     E = int(edge_index.shape[1])
     row = edge_index[0].to(torch.int64).contiguous()
@@ -2092,13 +2038,12 @@ def pool_edges(edge_index, sel):
     slot = torch.empty(E, dtype=torch.int64, device=dev)
     seg_ptr = torch.empty(E + 1, dtype=torch.int32, device=dev)
     seg_edge = torch.empty(E, dtype=torch.int32, device=dev)
-    wsb = lib.mp_cluster_edges_workspace(E, sel.n)
+    wsb = nat.mp_cluster_edges_workspace(E, sel.n)
     ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-    _lib.check(lib.mp_cluster_edges(row.data_ptr(), col.data_ptr(), E, sel.inv.data_ptr(), sel.n,
-                                    sel.counts.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), slot.data_ptr(),
-                                    E * 8, seg_ptr.data_ptr(), _lib.nbytes(seg_ptr), seg_edge.data_ptr(),
-                                    _lib.nbytes(seg_edge), ws.data_ptr(), wsb, _lib.stream_ptr(dev)),
-               "mp_cluster_edges")
+    nat.mp_cluster_edges(row.data_ptr(), col.data_ptr(), E, sel.inv.data_ptr(), sel.n, sel.counts.data_ptr(),
+                         out[0].data_ptr(), out[1].data_ptr(), slot.data_ptr(), E * 8, seg_ptr.data_ptr(),
+                         _lib.nbytes(seg_ptr), seg_edge.data_ptr(), _lib.nbytes(seg_edge), ws.data_ptr(), wsb,
+                         _lib.stream_ptr(dev))
     sel.M = sel.n_edges_out = None
     return EdgePooling(out, slot, seg_ptr, seg_edge, E)
 
@@ -2117,10 +2062,9 @@ class _PoolEdgeAttr(torch.autograd.Function):
         E, A = flat.shape
         out = torch.empty((E, A), dtype=torch.float32, device=attr.device)
         if E and A:
-            _lib.check(_lib.load().mp_cluster_edge_attr_f32(flat.data_ptr(), flat.stride(0), A, ep.seg_ptr.data_ptr(),
-                                                            ep.seg_edge.data_ptr(), sel.counts.data_ptr(), E,
-                                                            out.data_ptr(), A, _lib.nbytes(out),
-                                                            _lib.stream_ptr(attr.device)), "mp_cluster_edge_attr_f32")
+            _lib.native().mp_cluster_edge_attr_f32(flat.data_ptr(), flat.stride(0), A, ep.seg_ptr.data_ptr(),
+                                                   ep.seg_edge.data_ptr(), sel.counts.data_ptr(), E, out.data_ptr(), A,
+                                                   _lib.nbytes(out), _lib.stream_ptr(attr.device))
         ctx.ep, ctx.sel, ctx.shape = ep, sel, attr.shape
         return out.view((E,) + tuple(attr.shape[1:]))
 
@@ -2132,10 +2076,8 @@ class _PoolEdgeAttr(torch.autograd.Function):
         A = g.shape[1]
         ga = torch.empty((E, A), dtype=torch.float32, device=g.device)
         if E and A:
-            _lib.check(_lib.load().mp_cluster_edge_attr_bwd_f32(g.data_ptr(), A, ctx.ep.edge_slot.data_ptr(), E, A,
-                                                                kept, ga.data_ptr(), A, _lib.nbytes(ga),
-                                                                _lib.stream_ptr(g.device)),
-                       "mp_cluster_edge_attr_bwd_f32")
+            _lib.native().mp_cluster_edge_attr_bwd_f32(g.data_ptr(), A, ctx.ep.edge_slot.data_ptr(), E, A, kept,
+                                                       ga.data_ptr(), A, _lib.nbytes(ga), _lib.stream_ptr(g.device))
         return ga.view(ctx.shape), None, None
 
 

@@ -235,14 +235,13 @@ def _seg_starts(sizes, dev):
     return starts.to(dev)
 
 
-def _graph_ids(sizes, dev, lib, st):
+def _graph_ids(sizes, dev, nat, st):
     """torch.cat([torch.full((n_g,), g) for g, n_g in enumerate(sizes)]) on dev."""
-    from mi355_mp import _lib
     n = int(sum(sizes))
     ids = torch.empty(n, dtype=torch.long, device=dev)
     if n:
         starts = _seg_starts(sizes, dev)
-        _lib.check(lib.mp_segment_ids_i64(ids.data_ptr(), n, starts.data_ptr(), len(sizes), st), "mp_segment_ids_i64")
+        nat.mp_segment_ids_i64(ids.data_ptr(), n, starts.data_ptr(), len(sizes), st)
     return ids
 
 
@@ -258,7 +257,7 @@ def _collate_on_device(data_list, keys, follow_batch, dev):
     """Batch.from_data_list(data_list, follow_batch).to(dev), collated on dev
     (see Batch.from_data_list)."""
     from mi355_mp import _lib
-    lib = _lib.load()
+    nat = _lib.native()
     st = _lib.stream_ptr(dev)
     batch = Batch()
     ref = data_list[0] if data_list else Data()
@@ -294,8 +293,8 @@ def _collate_on_device(data_list, keys, follow_batch, dev):
                     # would go back to the caching allocator before the next allocation)
                     starts = _seg_starts(sizes, dev)
                     inc_d = torch.tensor(incs, dtype=torch.int64).to(dev)
-                    _lib.check(lib.mp_segment_offset_i64(d.data_ptr(), n, rows, n, starts.data_ptr(), inc_d.data_ptr(),
-                                                         len(items), st), "mp_segment_offset_i64")
+                    nat.mp_segment_offset_i64(d.data_ptr(), n, rows, n, starts.data_ptr(), inc_d.data_ptr(), len(items),
+                                              st)
                 else:
                     offs = torch.repeat_interleave(torch.tensor(incs, device=dev), torch.tensor(sizes, device=dev))
                     shape = [1] * d.dim()
@@ -309,12 +308,12 @@ def _collate_on_device(data_list, keys, follow_batch, dev):
             for g, sz in zip(gids, sizes):
                 fb[g] = sz
             # graphs without the key contribute no entries (as upstream's per-item torch.full)
-            batch["{}_batch".format(k)] = _graph_ids(fb, dev, lib, st)
+            batch["{}_batch".format(k)] = _graph_ids(fb, dev, nat, st)
     counts = [0] * len(data_list)
     for i, data in enumerate(data_list):
         n = data.num_nodes
         counts[i] = 0 if n is None else int(n)
-    batch.batch = _graph_ids(counts, dev, lib, st)
+    batch.batch = _graph_ids(counts, dev, nat, st)
     return batch.contiguous()
 
 
