@@ -147,13 +147,7 @@ struct AggArgs {
   int32_t F;
   int32_t n_cols;
   uint32_t x_bytes;  // extent of x for the scalar-batch buffer path (0: not used)
-  int32_t flat;      // sum/mean/max/min: run k_agg_flat instead of k_agg_main
-  int32_t fix4;      // VEC=2 main kernel: run the fix-up at VEC=4 (slabs are indexed by feature)
-  int32_t smem;      // flat sum/mean kernel: slot columns/weights through scalar loads (k_agg_flat SM)
   int32_t seq_tiles; // flat kernel: feature tiles one after another on all XCDs (no XCD-affine map)
-  int32_t far;       // flat SM kernel: x larger than the Infinity Cache (batches of kU_Vec1Far)
-  int32_t force_flat;  // mp_aggregate_tiles_f32: the scalar-batch flat kernel whatever the layout
-  int32_t xr;          // ... and its XR instance (tile-major operands, skipped rows, per-row bias)
   // features
   const float* w;
   const float* x;
@@ -648,7 +642,10 @@ __global__ __launch_bounds__(kBlock) void k_agg_fixup(AggArgs p) {
 }
 
 // ---------------------------------------------------------------------------
-// host side
+// host side.  Choosing and launching are separate: a unit names the kernels of
+// one aggregation as a value (AggLaunch: the main kernel, its grid, the
+// fix-up), and run() is the only function that launches one.  AggArgs holds
+// what the kernels read and nothing else.
 // ---------------------------------------------------------------------------
 
 struct Shape {
@@ -679,11 +676,6 @@ static inline Shape pick_shape(int F, int64_t ldx, const void* x, int64_t ldo, c
   return {vec, lanes};
 }
 
-// Every unit's main-stage launch goes through this one definition
-// (mp_aggregate.hip): under mp_aggregate_kernel_name's query it records the
-// kernel instead of launching it.
-int launch_main(void (*k)(AggArgs), dim3 grid, hipStream_t s, const AggArgs& a);
-
 // MP_TUNE_GAT_BWD_VEC of the one mp_tune table (mp_aggregate.hip)
 int64_t tuned_gat_bwd_vec();
 
@@ -704,28 +696,43 @@ static inline dim3 main_grid(const AggArgs& a) {
   return dim3((unsigned)nb, (unsigned)ftiles);
 }
 
-template <class Red, int VEC>
-static inline int launch_fixup(const AggArgs& a, hipStream_t s) {
-  dim3 grid((unsigned)a.n_split, (unsigned)ceil_div(a.F, 64 * VEC));
-  hipLaunchKernelGGL((k_agg_fixup<Red, VEC>), grid, dim3(kBlock), 0, s, a);
-  MP_CHECK_LAUNCH();
-  return MP_OK;
+// One aggregation's kernels, chosen on the host; nothing in it crosses to the device.
+using AggKernel = void (*)(AggArgs);
+struct AggLaunch {
+  AggKernel main;
+  dim3 main_grid;
+  AggKernel fixup;       // combines the split rows' partials, after main
+  unsigned fixup_tiles;  // grid.y of the fix-up; grid.x is a.n_split
+};
+
+// main and its grid, with the fix-up of reducer FixRed at FVEC features per lane
+template <class FixRed, int FVEC>
+static inline AggLaunch with_fixup(AggKernel main, dim3 grid, const AggArgs& a) {
+  return {main, grid, k_agg_fixup<FixRed, FVEC>, (unsigned)ceil_div(a.F, 64 * FVEC)};
 }
 
-// k_agg_main, then the fix-up of its split rows
+// k_agg_main with L-lane tasks, and the fix-up of its split rows
 template <class Red, int VEC, int L>
-static inline int launch_l(const AggArgs& a, int stages, hipStream_t s) {
+static inline AggLaunch engine_launch(const AggArgs& a) {
+  return with_fixup<Red, VEC>(k_agg_main<Red, VEC, kMainU<Red, VEC, L>, L>, main_grid<VEC, L>(a), a);
+}
+
+// The only place that launches: the stages asked for, the fix-up only when rows are split.
+static inline int run(const AggLaunch& l, const AggArgs& a, int stages, hipStream_t s) {
   if (stages & MP_STAGE_MAIN) {
-    int rc = launch_main(k_agg_main<Red, VEC, kMainU<Red, VEC, L>, L>, main_grid<VEC, L>(a), s, a);
-    if (rc) return rc;
+    hipLaunchKernelGGL(l.main, l.main_grid, dim3(kBlock), 0, s, a);
+    MP_CHECK_LAUNCH();
   }
-  if ((stages & MP_STAGE_FIXUP) && a.n_split > 0) return launch_fixup<Red, VEC>(a, s);
+  if ((stages & MP_STAGE_FIXUP) && a.n_split > 0) {
+    hipLaunchKernelGGL(l.fixup, dim3((unsigned)a.n_split, l.fixup_tiles), dim3(kBlock), 0, s, a);
+    MP_CHECK_LAUNCH();
+  }
   return MP_OK;
 }
 
 // fn(std::integral_constant<int, L>) for the task width `lanes` (VEC = 4: 4 .. 64, else 64)
 template <int VEC, class Fn>
-static inline int with_lanes(int lanes, Fn&& fn) {
+static inline auto with_lanes(int lanes, Fn&& fn) {
   if constexpr (VEC == 4) {
     switch (lanes) {
       case 4: return fn(std::integral_constant<int, 4>{});
@@ -738,9 +745,14 @@ static inline int with_lanes(int lanes, Fn&& fn) {
   return fn(std::integral_constant<int, 64>{});
 }
 
+// the engine's launch at the task width `lanes`, and that launch run
+template <class Red, int VEC>
+static inline AggLaunch engine_launch_at(int lanes, const AggArgs& a) {
+  return with_lanes<VEC>(lanes, [&](auto l) { return engine_launch<Red, VEC, decltype(l)::value>(a); });
+}
 template <class Red, int VEC>
 static inline int launch(const AggArgs& a, int stages, hipStream_t s, int lanes = 64) {
-  return with_lanes<VEC>(lanes, [&](auto l) { return launch_l<Red, VEC, decltype(l)::value>(a, stages, s); });
+  return run(engine_launch_at<Red, VEC>(lanes, a), a, stages, s);
 }
 
 static inline int64_t slab_ld_for(int F) { return ceil_div(F, 256) * 256; }

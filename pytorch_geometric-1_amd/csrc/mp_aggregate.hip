@@ -3,8 +3,11 @@
 // weighted sums (mp_aggregate_heads_f32) and the two-pass GAT
 // (mp_gat_softmax_aggregate_f32).  Besides the engine's k_agg_main it has two
 // main-stage kernels of its own, k_agg_lane (narrow rows, one task per lane)
-// and k_agg_flat (slot batches across row boundaries), the dispatch that
-// chooses between the three, and the mp_tune table.
+// and k_agg_flat (slot batches across row boundaries), and the mp_tune table.
+// choose() picks between the three: a pure host function of a call's arguments
+// and the table that returns the launch as a value (AggLaunch, mp_agg.h) and
+// launches nothing; the entry points are check, fill, choose, run, and
+// mp_aggregate_kernel_name is the same choice with its main kernel named.
 //   * sum uses separately-rounded mul and add (no FMA contraction) in original
 //     edge order, i.e. exactly the arithmetic of the reference's materialised
 //     `norm*x_j` followed by CPU scatter_add_: rows that fit in one task are
@@ -766,7 +769,7 @@ __global__ __launch_bounds__(kBlock) void k_agg_flat(AggArgs p) {
   }
 }
 
-// the same reducer at another lane width (fix-up of a VEC=2 main kernel at VEC=4)
+// the same reducer at another lane width (fix-up of a VEC < 4 flat kernel at VEC=4)
 template <class Red, int V>
 struct Rebind {
   using type = Red;
@@ -780,131 +783,105 @@ struct Rebind<ArgRed<VEC, W, M>, V> {
   using type = ArgRed<V, W, M>;
 };
 
-// Kernel query (mp_aggregate_kernel_name): while set, the main-stage launch
-// records the kernel the dispatcher chose instead of launching it.
-static thread_local bool g_query = false;
-static thread_local const void* g_query_kernel = nullptr;
-
-int launch_main(void (*k)(AggArgs), dim3 grid, hipStream_t s, const AggArgs& a) {
-  if (g_query) {
-    g_query_kernel = reinterpret_cast<const void*>(k);
-    return MP_OK;
-  }
-  hipLaunchKernelGGL(k, grid, dim3(kBlock), 0, s, a);
-  MP_CHECK_LAUNCH();
-  return MP_OK;
-}
+// What choose() settled about one sum / mean / max / min launch besides the
+// reducer and the lane shape; the ladder below turns it into kernels.
+struct FlatChoice {
+  bool flat = false;   // run k_agg_flat instead of k_agg_main (64-lane tasks)
+  bool smem = false;   // flat sum/mean kernel: slot columns/weights through scalar loads (k_agg_flat SM)
+  bool far = false;    // flat SM kernel: x larger than the Infinity Cache (batches of kU_Vec1Far)
+  bool tiles = false;  // mp_aggregate_tiles_f32: the SM kernel's XM / TM instance (tile-major operands,
+                       // skipped rows, per-row bias)
+  bool fixup4 = false; // VEC < 4 flat kernel: run the fix-up at VEC=4 (slabs are indexed by feature)
+};
 
 // the mp_aggregate_tiles_f32 instances: XM from the call (per-row bias flags /
 // skipped rows / neither), TM when an operand is tile-major
 template <class Red, int U, int XM>
-static int launch_xm(const AggArgs& a, dim3 grid, hipStream_t s, bool far) {
+static AggKernel flat_xm(const AggArgs& a, bool far) {
   const bool tm = a.x_tw || a.o_tw;
   if (tm)
-    return far ? launch_main(k_agg_flat<Red, 1, kU_Vec1Far, 64, false, true, XM, true>, grid, s, a)
-               : launch_main(k_agg_flat<Red, 1, U, 64, false, true, XM, true>, grid, s, a);
-  return far ? launch_main(k_agg_flat<Red, 1, kU_Vec1Far, 64, false, true, XM>, grid, s, a)
-             : launch_main(k_agg_flat<Red, 1, U, 64, false, true, XM>, grid, s, a);
+    return far ? k_agg_flat<Red, 1, kU_Vec1Far, 64, false, true, XM, true>
+               : k_agg_flat<Red, 1, U, 64, false, true, XM, true>;
+  return far ? k_agg_flat<Red, 1, kU_Vec1Far, 64, false, true, XM> : k_agg_flat<Red, 1, U, 64, false, true, XM>;
 }
 template <class Red, int U>
-static int launch_xr(const AggArgs& a, dim3 grid, hipStream_t s, bool far) {
-  if (a.bias_rows) return launch_xm<Red, U, 1>(a, grid, s, far);
-  if (a.flags & MP_FLAG_SKIP_EMPTY) return launch_xm<Red, U, 2>(a, grid, s, far);
-  return launch_xm<Red, U, 0>(a, grid, s, far);
+static AggKernel flat_tiles(const AggArgs& a, bool far) {
+  if (a.bias_rows) return flat_xm<Red, U, 1>(a, far);
+  if (a.flags & MP_FLAG_SKIP_EMPTY) return flat_xm<Red, U, 2>(a, far);
+  return flat_xm<Red, U, 0>(a, far);
 }
 
-// One sum / mean / max / min launch with L-lane tasks: k_agg_flat where the
-// dispatch chose it (a.flat: its smem / far / tile instances, and under a.fix4
-// the fix-up at VEC = 4), else the engine's k_agg_main and fix-up.
-template <class Red, int VEC, int L>
-static int launch_flat_l(const AggArgs& a, int stages, hipStream_t s) {
-  if (!a.flat) return launch_l<Red, VEC, L>(a, stages, s);
-  constexpr int U = kMainU<Red, VEC, L>;
-  if (stages & MP_STAGE_MAIN) {
-    const dim3 grid = main_grid<VEC, L>(a);
-    int rc = MP_OK;
-    if constexpr (L == 64 && !Red::kEid) {
-      bool far = false;
-      if constexpr (VEC == 1) {
-        far = a.smem && a.far;
-        if (far && !a.xr) rc = launch_main(k_agg_flat<Red, 1, kU_Vec1Far, 64, false, true>, grid, s, a);
-      }
-      if constexpr (VEC == 1) {
-        // mp_aggregate_tiles_f32 (scalar batches, 64-feature tiles by construction)
-        if (a.xr) rc = launch_xr<Red, U>(a, grid, s, far);
-      }
-      if (far || a.xr) {
-      } else if (a.smem) rc = launch_main(k_agg_flat<Red, VEC, U, 64, false, true>, grid, s, a);
-      else rc = launch_main(k_agg_flat<Red, VEC, U, L>, grid, s, a);
-    } else {
-      rc = launch_main(k_agg_flat<Red, VEC, U, L>, grid, s, a);
+// The k_agg_flat instance of one launch (64-lane tasks): its smem / far / tile
+// instances for sum and mean, the slot window for max and min.
+template <class Red, int VEC>
+static AggKernel flat_kernel(const AggArgs& a, const FlatChoice& c) {
+  constexpr int U = kMainU<Red, VEC, 64>;
+  if constexpr (!Red::kEid) {
+    if constexpr (VEC == 1) {
+      const bool far = c.smem && c.far;
+      // mp_aggregate_tiles_f32 (scalar batches, 64-feature tiles by construction)
+      if (c.tiles) return flat_tiles<Red, U>(a, far);
+      if (far) return k_agg_flat<Red, 1, kU_Vec1Far, 64, false, true>;
     }
-    if (rc) return rc;
+    if (c.smem) return k_agg_flat<Red, VEC, U, 64, false, true>;
   }
-  if ((stages & MP_STAGE_FIXUP) && a.n_split > 0) {
-    if constexpr (VEC != 4) {
-      if (a.fix4) return launch_fixup<typename Rebind<Red, 4>::type, 4>(a, s);
-    }
-    return launch_fixup<Red, VEC>(a, s);
-  }
-  return MP_OK;
+  return k_agg_flat<Red, VEC, U, 64>;
 }
 
 template <class Red, int VEC, int NV>
-static int launch_lane(const AggArgs& a, int stages, hipStream_t s) {
-  if (stages & MP_STAGE_MAIN) {
-    dim3 grid((unsigned)ceil_div(a.n_waves, kBlock));
-    constexpr int U = VEC * NV >= 16 ? (kULane + 1) / 2 : kULane;  // 16-float rows: keep VGPRs < 128
-    int rc = launch_main(k_agg_lane<Red, VEC, NV, U>, grid, s, a);
-    if (rc) return rc;
-  }
-  if ((stages & MP_STAGE_FIXUP) && a.n_split > 0) return launch_fixup<Red, VEC>(a, s);
-  return MP_OK;
+static AggLaunch lane_launch(const AggArgs& a) {
+  constexpr int U = VEC * NV >= 16 ? (kULane + 1) / 2 : kULane;  // 16-float rows: keep VGPRs < 128
+  return with_fixup<Red, VEC>(k_agg_lane<Red, VEC, NV, U>, dim3((unsigned)ceil_div(a.n_waves, kBlock)), a);
 }
 
-// lane-task shape for F <= kLaneMaxF: VEC=4 with NV in {1,2,4} or VEC=1
-// with NV in {4,8,16}; -1 when the row is too wide
+// One sum / mean / max / min launch of reducer Red at VEC features per lane:
+// lane tasks for F <= kLaneMaxF (VEC=4 with NV in {1,2} or VEC=1 with NV in
+// {4,8}), k_agg_flat where the choice is flat (under c.fixup4 with the fix-up at
+// VEC = 4), else the engine's k_agg_main with `lanes`-lane tasks and its fix-up.
 template <class Red, int VEC>
-static int try_lane(const AggArgs& a, int stages, hipStream_t s) {
-  if (a.F > kLaneMaxF || a.F < 2) return -1;
-  if constexpr (VEC == 4) {
-    if (a.F <= 4) return launch_lane<Red, 4, 1>(a, stages, s);
-    return launch_lane<Red, 4, 2>(a, stages, s);
-  } else if constexpr (VEC == 1) {
-    if (a.F <= 4) return launch_lane<Red, 1, 4>(a, stages, s);
-    return launch_lane<Red, 1, 8>(a, stages, s);
-  }
-  return -1;
-}
-
-template <class Red, int VEC>
-static int launch_any(const AggArgs& a, int stages, hipStream_t s, int L) {
+static AggLaunch launch_of(const AggArgs& a, const FlatChoice& c, int lanes) {
   if constexpr (VEC != 2) {
-    int rc = try_lane<Red, VEC>(a, stages, s);
-    if (rc >= 0) return rc;
+    if (a.F <= kLaneMaxF && a.F >= 2) {
+      if constexpr (VEC == 4) return a.F <= 4 ? lane_launch<Red, 4, 1>(a) : lane_launch<Red, 4, 2>(a);
+      else return a.F <= 4 ? lane_launch<Red, 1, 4>(a) : lane_launch<Red, 1, 8>(a);
+    }
   }
-  return with_lanes<VEC>(L, [&](auto l) { return launch_flat_l<Red, VEC, decltype(l)::value>(a, stages, s); });
+  if (!c.flat) return engine_launch_at<Red, VEC>(lanes, a);
+  const AggKernel k = flat_kernel<Red, VEC>(a, c);
+  const dim3 grid = main_grid<VEC, 64>(a);
+  if constexpr (VEC != 4) {
+    if (c.fixup4) return with_fixup<typename Rebind<Red, 4>::type, 4>(k, grid, a);
+  }
+  return with_fixup<Red, VEC>(k, grid, a);
 }
 
+// reduce is one of the four (the callers checked)
 template <int VEC>
-static int dispatch_reduce(const AggArgs& a, int reduce, int stages, hipStream_t s, int L) {
+static AggLaunch launch_of_reduce(const AggArgs& a, int reduce, const FlatChoice& c, int lanes) {
   const bool hw = a.w != nullptr;
   switch (reduce) {
     case MP_REDUCE_SUM:
-      return hw ? launch_any<SumRed<VEC, true, false>, VEC>(a, stages, s, L)
-                : launch_any<SumRed<VEC, false, false>, VEC>(a, stages, s, L);
+      return hw ? launch_of<SumRed<VEC, true, false>, VEC>(a, c, lanes)
+                : launch_of<SumRed<VEC, false, false>, VEC>(a, c, lanes);
     case MP_REDUCE_MEAN:
-      return hw ? launch_any<SumRed<VEC, true, true>, VEC>(a, stages, s, L)
-                : launch_any<SumRed<VEC, false, true>, VEC>(a, stages, s, L);
+      return hw ? launch_of<SumRed<VEC, true, true>, VEC>(a, c, lanes)
+                : launch_of<SumRed<VEC, false, true>, VEC>(a, c, lanes);
     case MP_REDUCE_MAX:
-      return hw ? launch_any<ArgRed<VEC, true, true>, VEC>(a, stages, s, L)
-                : launch_any<ArgRed<VEC, false, true>, VEC>(a, stages, s, L);
-    case MP_REDUCE_MIN:
-      return hw ? launch_any<ArgRed<VEC, true, false>, VEC>(a, stages, s, L)
-                : launch_any<ArgRed<VEC, false, false>, VEC>(a, stages, s, L);
+      return hw ? launch_of<ArgRed<VEC, true, true>, VEC>(a, c, lanes)
+                : launch_of<ArgRed<VEC, false, true>, VEC>(a, c, lanes);
+    default:  // MP_REDUCE_MIN
+      return hw ? launch_of<ArgRed<VEC, true, false>, VEC>(a, c, lanes)
+                : launch_of<ArgRed<VEC, false, false>, VEC>(a, c, lanes);
   }
-  set_error("mp_aggregate_f32: unknown reduce %d", reduce);
-  return MP_ERR_ARG;
+}
+
+// A statistics pass of the two-pass GAT over x = a_src [N, H] (F = H): k_agg_main
+// lane groups, one lane per head: H <= 4 -> 4 lanes, <= 8 -> 8, else 16
+template <class Red>
+static AggLaunch gat_stats_launch(const AggArgs& t) {
+  if (t.H <= 4) return engine_launch<Red, 1, 4>(t);
+  if (t.H <= 8) return engine_launch<Red, 1, 8>(t);
+  return engine_launch<Red, 1, 16>(t);
 }
 
 // ---------------------------------------------------------------------------
@@ -949,18 +926,22 @@ static inline int64_t tuned(std::atomic<int64_t>& v) { return v.load(std::memory
 int64_t tuned_gat_bwd_vec() { return tuned(g_tune.gat_bwd_vec); }
 int64_t tuned_topk_wg_limit() { return tuned(g_tune.topk_wg_limit); }
 
-// Shape selection and launch of one mp_aggregate_f32 call (args checked).
-static int aggregate_dispatch(AggArgs& a, const mp_csr* g, int reduce, int stages, hipStream_t s) {
+// The kernels of one mp_aggregate_f32 call (tiles: of one mp_aggregate_tiles_f32
+// call), args checked: a pure function of the arguments and the mp_tune table.
+// It launches nothing; of `a` it sets the two fields the flat kernel reads on
+// the device, x_bytes and seq_tiles.
+static AggLaunch choose(AggArgs& a, const mp_csr* g, int reduce, bool tiles = false) {
   const int F = a.F;
   const bool is_arg = reduce == MP_REDUCE_MAX || reduce == MP_REDUCE_MIN;
-  if (a.x_tw || a.o_tw || a.force_flat) {
+  FlatChoice c;
+  if (tiles) {
     // tile-major operands (mp_aggregate_tiles_f32, arguments checked there): the
     // scalar-batch flat kernel with 64-feature tiles, its fix-up 64 wide
     const int64_t xbytes = (int64_t)g->n_cols * (a.x_tw ? a.x_tw : a.ldx) * 4;
-    a.flat = 1;
-    a.smem = 1;
+    c.flat = true;
+    c.smem = true;
     a.x_bytes = (uint32_t)xbytes;
-    a.far = xbytes > tuned(g_tune.flat_far_min_bytes) ? 1 : 0;
+    c.far = xbytes > tuned(g_tune.flat_far_min_bytes);
     // feature tiles one after another when x outgrows the Infinity Cache by up to 4x: then
     // each 64-feature tile of it (a quarter) fits, and the tiles take turns in it (the
     // sharded step's P = 4 passes: interior 0.68 -> 0.65 ms, send 1.26 -> 1.22 ms; at P = 8,
@@ -968,9 +949,8 @@ static int aggregate_dispatch(AggArgs& a, const mp_csr* g, int reduce, int stage
     const int64_t x_all = (int64_t)g->n_cols * F * 4;
     a.seq_tiles = (tuned(g_tune.flat_seq_tiles) || (x_all > kSeqTilesMin && x_all <= 4 * tuned(g_tune.flat_far_min_bytes)))
                       ? 1 : 0;
-    a.fix4 = 0;
-    a.xr = 1;
-    return dispatch_reduce<1>(a, reduce, stages, s, 64);
+    c.tiles = true;
+    return launch_of_reduce<1>(a, reduce, c, 64);
   }
   Shape sh = pick_shape(F, a.ldx, a.x, a.ldo, a.out);
   // flat kernel lane width: 64-feature tiles (VEC=1) for sum/mean, where an
@@ -997,26 +977,26 @@ static int aggregate_dispatch(AggArgs& a, const mp_csr* g, int reduce, int stage
   // (Max/min through the same batches, edge ids included: bitwise equal and
   // no faster -- Reddit-scale 8.67 vs 8.67 ms, RMAT21 7.77 vs 7.76 ms,
   // profiles/r02_ab_smem_arg.log -- so they keep the slot window.)
-  a.smem = tuned(g_tune.flat_smem) && !is_arg && a.col != nullptr && g->n_cols > 0 && xbytes <= 0xFFFFFFF0LL;
-  if (a.smem) a.x_bytes = (uint32_t)xbytes;
+  c.smem = tuned(g_tune.flat_smem) && !is_arg && a.col != nullptr && g->n_cols > 0 && xbytes <= 0xFFFFFFF0LL;
+  if (c.smem) a.x_bytes = (uint32_t)xbytes;
   // In-flight depth of the scalar-batch kernel: 16 row loads per wave while x
   // fits the Infinity Cache (Reddit-scale, 238 MB: 7.25 ms vs 7.64 at 8); 8
   // beyond it (RMAT21 6.71 -> 6.58 ms, ogbn-products-scale 15.0 -> 14.6 ms;
   // profiles/r02_ab_batch_u.log)
-  a.far = xbytes > tuned(g_tune.flat_far_min_bytes) ? 1 : 0;
+  c.far = xbytes > tuned(g_tune.flat_far_min_bytes);
   a.seq_tiles = (int32_t)tuned(g_tune.flat_seq_tiles);
   const int64_t min_f = is_arg ? tuned(g_tune.flat_min_f_arg) : tuned(g_tune.flat_min_f);
   if (F >= min_f && F % fvec == 0 && sh.vec >= fvec) {
     sh.vec = fvec;  // narrow feature tiles, slot batches across rows
     sh.lanes = 64;
-    a.flat = 1;
+    c.flat = true;
     // the fix-up reads slabs by feature: run it 4 wide when out (and bias) allow
-    a.fix4 = F % 4 == 0 && (uintptr_t)a.out % 16 == 0 && a.ldo % 4 == 0 && (uintptr_t)a.bias % 16 == 0;
+    c.fixup4 = F % 4 == 0 && (uintptr_t)a.out % 16 == 0 && a.ldo % 4 == 0 && (uintptr_t)a.bias % 16 == 0;
   }
   switch (sh.vec) {
-    case 4: return dispatch_reduce<4>(a, reduce, stages, s, sh.lanes);
-    case 2: return dispatch_reduce<2>(a, reduce, stages, s, 64);
-    default: return dispatch_reduce<1>(a, reduce, stages, s, 64);
+    case 4: return launch_of_reduce<4>(a, reduce, c, sh.lanes);
+    case 2: return launch_of_reduce<2>(a, reduce, c, 64);
+    default: return launch_of_reduce<1>(a, reduce, c, 64);
   }
 }
 
@@ -1058,6 +1038,7 @@ int mp_aggregate_f32(const mp_csr* g, const float* w, const float* x, int64_t ld
   MP_CHECK_ARG(slab != nullptr && slab_bytes >= mp_aggregate_slab_bytes(g, F, reduce),
                "mp_aggregate_f32: slab workspace too small (%zu < %zu)", slab_bytes,
                mp_aggregate_slab_bytes(g, F, reduce));
+  MP_CHECK_ARG(reduce >= MP_REDUCE_SUM && reduce <= MP_REDUCE_MIN, "mp_aggregate_f32: unknown reduce %d", reduce);
   AggArgs a{};
   fill_graph(a, g);
   a.F = F;
@@ -1070,7 +1051,7 @@ int mp_aggregate_f32(const mp_csr* g, const float* w, const float* x, int64_t ld
   a.ldo = ldo;
   a.arg_out = arg_out;
   carve_slabs(a, slab, is_arg ? kSlabArg : 0);
-  return aggregate_dispatch(a, g, reduce, stages, as_stream(stream));
+  return run(choose(a, g, reduce), a, stages, as_stream(stream));
 }
 
 int mp_aggregate_tiles_f32(const mp_csr* g, const float* w, const float* x, int64_t ldx, int32_t x_tile_w,
@@ -1129,9 +1110,8 @@ int mp_aggregate_tiles_f32(const mp_csr* g, const float* w, const float* x, int6
   // every call takes the scalar-batch flat kernel with 64-feature tiles (its
   // instance chosen by the operands' layout and the call's options), row-major
   // operands included: the same kernel mp_aggregate_f32 picks for such rows,
-  // with the feature-tile order chosen for the pass's x (see aggregate_dispatch)
-  a.force_flat = 1;
-  return aggregate_dispatch(a, g, reduce, stages, as_stream(stream));
+  // with the feature-tile order chosen for the pass's x (see choose)
+  return run(choose(a, g, reduce, true), a, stages, as_stream(stream));
 }
 
 int mp_aggregate_kernel_name(const mp_csr* g, const float* w, const float* x, int64_t ldx, int32_t F,
@@ -1152,13 +1132,8 @@ int mp_aggregate_kernel_name(const mp_csr* g, const float* w, const float* x, in
   a.bias = bias;
   a.out = const_cast<float*>(out);
   a.ldo = ldo;
-  g_query = true;
-  g_query_kernel = nullptr;
-  rc = aggregate_dispatch(a, g, reduce, MP_STAGE_MAIN, as_stream(stream));
-  g_query = false;
-  if (rc) return rc;
-  MP_CHECK_ARG(g_query_kernel != nullptr, "mp_aggregate_kernel_name: no main kernel selected");
-  const char* mangled = hipKernelNameRefByPtr(g_query_kernel, as_stream(stream));
+  const char* mangled = hipKernelNameRefByPtr(reinterpret_cast<const void*>(choose(a, g, reduce).main),
+                                             as_stream(stream));
   MP_CHECK_ARG(mangled != nullptr, "mp_aggregate_kernel_name: HIP has no name for the kernel (no device?)");
   int st = 0;
   char* dem = abi::__cxa_demangle(mangled, nullptr, nullptr, &st);
@@ -1239,14 +1214,10 @@ int mp_gat_softmax_aggregate_f32(const mp_csr* g, const int32_t* slot_row, const
     t.x = a_src;
     t.ldx = H;
     t.slab_ld = slab_ld_for(H);
-    for (int pass = 0; pass < 2; ++pass) {
-      // k_agg_main lane groups, one lane per head: H <= 4 -> 4 lanes, <= 8 -> 8, else 16
-      // (t.flat is 0; the plain launcher keeps the flat instances these calls have always built)
-      if (H <= 4) rc = pass ? launch_flat_l<GatDenRed<1>, 1, 4>(t, MP_STAGE_ALL, s) : launch_flat_l<GatMaxRed<1>, 1, 4>(t, MP_STAGE_ALL, s);
-      else if (H <= 8) rc = pass ? launch_flat_l<GatDenRed<1>, 1, 8>(t, MP_STAGE_ALL, s) : launch_flat_l<GatMaxRed<1>, 1, 8>(t, MP_STAGE_ALL, s);
-      else rc = pass ? launch_flat_l<GatDenRed<1>, 1, 16>(t, MP_STAGE_ALL, s) : launch_flat_l<GatMaxRed<1>, 1, 16>(t, MP_STAGE_ALL, s);
-      if (rc) return rc;
-    }
+    rc = run(gat_stats_launch<GatMaxRed<1>>(t), t, MP_STAGE_ALL, s);
+    if (rc) return rc;
+    rc = run(gat_stats_launch<GatDenRed<1>>(t), t, MP_STAGE_ALL, s);
+    if (rc) return rc;
   }
   a.F = F;
   a.w = a_src;  // any non-null pointer: the HAS_W reducer multiplies by the window's alpha
@@ -1256,18 +1227,13 @@ int mp_gat_softmax_aggregate_f32(const mp_csr* g, const int32_t* slot_row, const
   a.out = out;
   a.ldo = ldo;
   a.slab_ld = slab_ld_for(F);
-  a.flat = 1;
+  // the GA instance of k_agg_flat; its fix-up 4 wide when out (and bias) allow
   using Red = SumRed<1, true, false>;
-  if ((stages & MP_STAGE_MAIN) && a.n_waves > 0) {
-    hipLaunchKernelGGL((k_agg_flat<Red, 1, kU_Vec1, 64, true>), (main_grid<1, 64>(a)), dim3(kBlock), 0, s, a);
-    MP_CHECK_LAUNCH();
-  }
-  if ((stages & MP_STAGE_FIXUP) && a.n_split > 0) {
-    if (F % 4 == 0 && (uintptr_t)out % 16 == 0 && ldo % 4 == 0 && (uintptr_t)bias % 16 == 0)
-      return launch_fixup<SumRed<4, true, false>, 4>(a, s);
-    return launch_fixup<Red, 1>(a, s);
-  }
-  return MP_OK;
+  const AggKernel k = k_agg_flat<Red, 1, kU_Vec1, 64, true>;
+  const bool fix4 = F % 4 == 0 && (uintptr_t)out % 16 == 0 && ldo % 4 == 0 && (uintptr_t)bias % 16 == 0;
+  return run(fix4 ? with_fixup<SumRed<4, true, false>, 4>(k, main_grid<1, 64>(a), a)
+                  : with_fixup<Red, 1>(k, main_grid<1, 64>(a), a),
+             a, stages, s);
 }
 
 }  // extern "C"
