@@ -852,6 +852,71 @@ int mp_cluster_edge_attr_f32(const float* attr, int64_t lda, int32_t A, const in
 int mp_cluster_edge_attr_bwd_f32(const float* g, int64_t ldg, const int64_t* edge_slot, int64_t n_edges, int32_t A,
                                  int64_t n_out, float* g_attr, int64_t ldga, size_t g_attr_bytes, void* stream);
 
+/* ---- Graclus (csrc/mp_graclus.hip) --------------------------------------------
+ * PyG 1.4.3 nn.pool.graclus [U] (torch_cluster 1.5 graclus_cluster) as a
+ * deterministic greedy matching: a pure function of the graph, where upstream's
+ * propose / respond rounds depend on a random node order.
+ *
+ * Pairs.  Edge e = (row[e], col[e]) with row != col is an entry of the unordered
+ * pair (a, b), a = min, b = max; loops are ignored, the direction does not
+ * matter, an edge present one way only still joins its pair.
+ *
+ * Priority of an entry: the tuple (wkey, h, a, b), compared lexicographically,
+ * the larger wins.
+ *   wkey = the order-preserving uint32 image of the fp32 weight: with u its bits,
+ *          u >> 31 ? ~u : u | 0x80000000 (so -0.0 < +0.0); 0 when weight is NULL;
+ *   h    = the upper 32 bits of mix64(mix64(seed) ^ ((a << 32) | b)), mix64 the
+ *          splitmix64 finaliser  z += 0x9E3779B97F4A7C15;
+ *          z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;
+ *          z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z ^ (z >> 31)   (mod 2^64).
+ * Distinct pairs never compare equal; the entries of one pair differ at most in
+ * wkey, so a pair carries the largest weight among its entries of either
+ * direction.  NaN weights are outside the contract.
+ *
+ * Matching.  Walk the entries in descending priority and match (a, b) when both
+ * ends are unmatched: cluster[a] = cluster[b] = a; cluster[i] = i for every other
+ * node (int64 [n], every entry written).  The kernels compute it in rounds: every
+ * live node points at its best entry among unmatched neighbours, mutual pointers
+ * match, and a node with no unmatched neighbour left drops out; the order being
+ * strict, the result equals the serial walk exactly and depends on neither the
+ * launch shape nor the order of the edges.  Hashed priorities take O(log n)
+ * rounds in expectation; a path whose weights increase strictly along it takes
+ * one round per matched pair.
+ *
+ * The caller builds the node-sorted incidence list of the 2 * n_edges directed
+ * entries with mp_csr_build(key = cat(row, col), other = cat(col, row), 2 *
+ * n_edges, n, n): rowptr [n + 1], nbr [2 * n_edges] (= its col) and eid
+ * [2 * n_edges] (the entry's position in the concatenation), all int32.
+ * n, n_edges < 2^30.  counts (int64[4], device): [0] = rounds run, [1 + (r & 1)] =
+ * nodes still live after round r (the nodes with an entry that is no loop count
+ * as live before round 0, in [2]), [3] = entries whose position or ends lie
+ * outside their range (the caller raises).  ws: mp_graclus_workspace(n, n_edges)
+ * bytes, the same block for mp_graclus_init and every mp_graclus_rounds after it.
+ *
+ * mp_graclus_init: zeroes counts, writes cluster[i] = i, the priority word of every
+ *   incidence entry and the live nodes into ws.  weight: fp32 [n_edges] or NULL.
+ * mp_graclus_rounds: enqueues rounds first_round .. first_round + n_rounds - 1
+ *   (two launches each; n_rounds <= 4096) after mp_graclus_init or an earlier
+ *   batch.  A round whose predecessor left nobody live returns at once and is
+ *   not counted, so the caller enqueues a batch, reads counts once, and stops
+ *   when the slot of the batch's last round is 0.  No grid is capped.
+ *
+ * Both return int64_t, not a status: the number of launches (init) or rounds
+ * (rounds) enqueued, >= 0, or -(MP_ERR_* code) with the reason in mp_last_error()
+ * when the call is refused -- for a bad argument, before any launch.  They are
+ * therefore not among the `int` status symbols a binding may wrap to raise: the
+ * caller tests the sign itself.  The entry points are additions: the ABI version
+ * is unchanged. */
+size_t mp_graclus_workspace(int64_t n, int64_t n_edges);
+int64_t mp_graclus_init(const int64_t* row, const int64_t* col, const float* weight, size_t weight_bytes,
+                        int64_t n_edges, int64_t n, uint64_t seed, const int32_t* eid, size_t eid_bytes,
+                        int64_t* cluster, size_t cluster_bytes, int64_t* counts, size_t counts_bytes, void* ws,
+                        size_t ws_bytes, void* stream);
+int64_t mp_graclus_rounds(const int32_t* rowptr, size_t rowptr_bytes, const int32_t* nbr, size_t nbr_bytes,
+                          int64_t n_edges, int64_t n, int64_t first_round, int64_t n_rounds, int64_t* cluster,
+                          size_t cluster_bytes, int64_t* counts, size_t counts_bytes, void* ws, size_t ws_bytes,
+                          void* stream);
+
 /* ---- other dtypes (csrc/mp_dtype.hip) -------------------------------------
  * torch_scatter 2.0.4 reduces any dtype ([U8/U9]); the fp32 hot path is
  * mp_aggregate_f32, these are the breadth path for the rest. */

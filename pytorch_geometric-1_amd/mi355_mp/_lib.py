@@ -190,6 +190,10 @@ SIGNATURES = {
                                         c_p]),
     "mp_cluster_edge_attr_f32": (ctypes.c_int, [c_p, i64, i32, c_p, c_p, c_p, i64, c_p, i64, sz, c_p]),
     "mp_cluster_edge_attr_bwd_f32": (ctypes.c_int, [c_p, i64, c_p, i64, i32, i64, c_p, i64, sz, c_p]),
+    "mp_graclus_workspace": (sz, [i64, i64]),
+    # these two return int64: a count >= 0, or -(code); the caller tests the sign (ops.graclus_match)
+    "mp_graclus_init": (i64, [c_p, c_p, c_p, sz, i64, i64, u64, c_p, sz, c_p, sz, c_p, sz, c_p, sz, c_p]),
+    "mp_graclus_rounds": (i64, [c_p, sz, c_p, sz, i64, i64, i64, i64, c_p, sz, c_p, sz, c_p, sz, c_p]),
 }
 
 # Of the symbols declared `int` / `int32_t`, these answer a question (a version,

@@ -2094,3 +2094,109 @@ def pool_edge_attr_sum(edge_attr, ep, sel):
     if edge_attr.numel() == 0:
         return edge_attr          # no edges (or no columns): the empty selection, as upstream's edge_attr[mask]
     return _PoolEdgeAttr.apply(edge_attr, ep, sel)
+
+
+# Rounds enqueued per host read of graclus_match.  Measured (profiles/graclus_bench.json):
+# the 64 x 75 superpixel-shaped batch takes 6 rounds unweighted and 9 with normalized-cut
+# weights, the 2^20-node graph 10 and 13, so 8 covers them in one or two reads.  A round
+# whose predecessor left nobody live is two launches that return at once; 16 per read
+# saves the second read and pays for it in such launches (the same time within 1 %
+# summed over the four cases), one round per read is 3 to 34 % slower.
+GRACLUS_ROUNDS_PER_READ = 8
+
+
+class GraclusMatching(object):
+    """What graclus_match leaves: cluster [n] int64 on the device, and on the
+    host the rounds the matching took, the device-to-host reads of the call and
+    the launches the mp_graclus_* entry points enqueued (skipped rounds included)."""
+    __slots__ = ("cluster", "rounds", "host_reads", "launches")
+
+    def __init__(self, cluster, rounds, host_reads, launches):
+        self.cluster, self.rounds, self.host_reads, self.launches = cluster, rounds, host_reads, launches
+
+
+def _graclus_call(nat, name, *args):
+    """The mp_graclus_* entry points return a count, or -(code): they are not
+    among the status symbols native() wraps, so the sign is tested here."""
+    rc = getattr(nat, name)(*args)
+    if rc < 0:
+        raise RuntimeError("%s failed (code %d): %s" % (name, -rc, nat.mp_last_error().decode(errors="replace")))
+    return rc
+
+
+def graclus_incidence(edge_index, n):
+    """(row, col, rowptr, nbr, eid) of the node-sorted incidence list of the 2E
+    directed entries of edge_index: mp_csr_build over cat(row, col) / cat(col, row),
+    int32.  No host read: graclus_match reads the ends' range check with its counts."""
+    nat = _lib.native()
+    dev = edge_index.device
+    E = int(edge_index.shape[1])
+    row = edge_index[0].contiguous()
+    col = edge_index[1].contiguous()
+    rowptr = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    nbr = torch.empty(2 * E, dtype=torch.int32, device=dev)
+    eid = torch.empty(2 * E, dtype=torch.int32, device=dev)
+    bad = torch.empty(1, dtype=torch.int32, device=dev)
+    wsb = nat.mp_csr_build_workspace(2 * E, n)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    ends = torch.cat([row, col]) if E else None
+    others = torch.cat([col, row]) if E else None
+    nat.mp_csr_build(_lib.ptr(ends), _lib.ptr(others), 2 * E, n, n, rowptr.data_ptr(), _lib.ptr(nbr if E else None), _lib.ptr(eid if E else None),
+                     bad.data_ptr(), ws.data_ptr(), wsb, _lib.stream_ptr(dev))
+    return row, col, rowptr, nbr, eid
+
+
+def graclus_match(edge_index, weight, n, seed=0, rounds_per_read=None):
+    """The deterministic greedy matching of include/mi355_mp.h "Graclus" as a
+    GraclusMatching: edge_index int64 [2, E], weight float32 [E] or None, n nodes.
+
+    One node-sorted incidence list of the 2E directed entries (mp_csr_build),
+    mp_graclus_init, then batches of rounds_per_read rounds (default
+    GRACLUS_ROUNDS_PER_READ) with one host read of the counts after each, until a
+    batch's last round leaves no node live: max(1, ceil(rounds / rounds_per_read))
+    reads, none when there is no edge.  The incidence build's index check is read
+    with the first batch.  An edge end outside [0, n) raises IndexError."""
+    _lib.require_device(edge_index, weight)
+    if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.shape[0] != 2:
+        raise ValueError("mi355_mp: edge_index must be int64 [2, E] (got %s %s)"
+                         % (edge_index.dtype, tuple(edge_index.shape)))
+    n, E = int(n), int(edge_index.shape[1])
+    if weight is not None:
+        if weight.dtype != torch.float32:
+            raise TypeError("mi355_mp: graclus weights must be float32 (got %s)" % weight.dtype)
+        if weight.dim() != 1 or weight.shape[0] != E:
+            raise ValueError("mi355_mp: weight must be [%d] (got %s)" % (E, tuple(weight.shape)))
+        weight = weight.detach().contiguous()
+    if n < 0 or n >= 1 << 30 or E >= 1 << 30:
+        raise ValueError("mi355_mp: graclus takes fewer than 2^30 nodes and edges (got %d, %d)" % (n, E))
+    if n == 0 and E:
+        raise IndexError("graclus: %d edge ends lie outside [0, 0)" % (2 * E))
+    R = int(GRACLUS_ROUNDS_PER_READ if rounds_per_read is None else rounds_per_read)
+    if R < 1:
+        raise ValueError("mi355_mp: rounds_per_read must be at least 1")
+    nat = _lib.native()
+    dev = edge_index.device
+    st = _lib.stream_ptr(dev)
+    row, col, rowptr, nbr, eid = graclus_incidence(edge_index, n)
+    cluster = torch.empty(n, dtype=torch.int64, device=dev)
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    gwb = nat.mp_graclus_workspace(n, E)
+    gws = torch.empty(gwb, dtype=torch.uint8, device=dev)
+    tail = (_lib.ptr(cluster if n else None), _lib.nbytes(cluster), counts.data_ptr(), _lib.nbytes(counts),
+            gws.data_ptr(), gwb, st)
+    launches = _graclus_call(nat, "mp_graclus_init", _lib.ptr(row if E else None), _lib.ptr(col if E else None),
+                             _lib.ptr(weight), _lib.nbytes(weight), E, n, int(seed) & _MASK64,
+                             _lib.ptr(eid if E else None), _lib.nbytes(eid), *tail)
+    rounds = reads = first = 0
+    while E:
+        launches += 2 * _graclus_call(nat, "mp_graclus_rounds", rowptr.data_ptr(), _lib.nbytes(rowptr), nbr.data_ptr(),
+                                      _lib.nbytes(nbr), E, n, first, R, *tail)
+        first += R
+        got = counts.tolist()
+        reads += 1
+        if got[3]:
+            raise IndexError("graclus: %d edges have an end outside [0, %d)" % (got[3] // 2, n))
+        rounds = got[0]
+        if got[1 + ((first - 1) & 1)] == 0:
+            break
+    return GraclusMatching(cluster, rounds, reads, launches)

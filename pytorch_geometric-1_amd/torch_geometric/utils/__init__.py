@@ -6,6 +6,8 @@ from .loop import (contains_self_loops, remove_self_loops, add_self_loops,
 from .degree import degree
 from .get_laplacian import get_laplacian
 from .repeat import repeat
+from .normalized_cut import normalized_cut
 
 __all__ = ["maybe_num_nodes", "scatter_", "softmax", "contains_self_loops", "remove_self_loops",
-           "add_self_loops", "add_remaining_self_loops", "degree", "get_laplacian", "repeat"]
+           "add_self_loops", "add_remaining_self_loops", "degree", "get_laplacian", "repeat",
+           "normalized_cut"]
