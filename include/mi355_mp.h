@@ -917,6 +917,76 @@ int64_t mp_graclus_rounds(const int32_t* rowptr, size_t rowptr_bytes, const int3
                           size_t cluster_bytes, int64_t* counts, size_t counts_bytes, void* ws, size_t ws_bytes,
                           void* stream);
 
+/* ---- Point sets: fps, radius, PointConv's edge features (csrc/mp_point.hip) ----
+ * The geometry of PyG 1.4.3's PointNet++ set abstraction (nn.fps / nn.radius over
+ * torch_cluster 1.5, nn.conv.PointConv [U]) as pure functions of their inputs;
+ * tests/_point_ref.py restates them in numpy.  No float is added atomically
+ * (the one atomic is an integer count), there is no CPU path, and every index
+ * read from device memory is bounded before it is used.  The entry points are
+ * additions: the ABI version is unchanged.
+ *
+ * Squared distance, D = 1..8 columns, fp32, every operation rounded, nothing
+ * contracted, left to right:
+ *     acc = (a_0 - b_0) * (a_0 - b_0);  acc = acc + (a_d - b_d) * (a_d - b_d), d = 1..D-1
+ *
+ * mp_fps_f32: farthest point sampling, one workgroup (or wave) per graph.
+ *   starts [G + 1]: the graphs' rows of pos (mp_batch_starts); out_starts [G + 1]:
+ *   the exclusive scan of k_g (mp_topk_counts: k_g = ceil(fl32(ratio * fl32(n_g))));
+ *   start [G] int64: the in-graph offset of each graph's first point, or NULL = 0.
+ *   idx[out_starts[g] + t] = the t-th point graph g selects, as a row of pos:
+ *   t = 0 is starts[g] + start[g]; then m[i] = d < m[i] ? d : m[i] (from +inf) with
+ *   d the squared distance of point i to the last selection, and the next one is
+ *   the argmax of m, equal values to the lower index.  A graph with fewer distinct
+ *   points than k_g selects points twice.  Non-finite coordinates never fault and
+ *   never select outside the graph; what they select is unspecified.
+ *   counts (int64[4], device): [0] is left alone (mp_topk_counts wrote K there),
+ *   [1] = graphs whose start lies outside [0, n_g) (they start at 0; the caller
+ *   raises); a graph of no points ignores its start.
+ *   mp_fps_path(n_g): 0 = one wave, m and the points in registers, no barrier
+ *   (n_g <= MP_FPS_WAVE_LIMIT, default 256); 1 = one workgroup, registers, one
+ *   barrier per step (n_g <= MP_FPS_BLOCK_LIMIT, default 8192); 2 = one workgroup,
+ *   m in the workspace; it answers a question and returns int64_t, so it is not among
+ *   the `int` status symbols a binding wraps to raise.  max_n: the largest graph (it picks the launches and the
+ *   workspace: mp_fps_workspace(n, max_n) bytes; a graph above it is left unsampled).
+ *
+ * mp_radius_search_f32 / mp_radius_fill: for every row j of y the first `cap`
+ *   rows i of x, ascending, of the same graph with d2(x_i, y_j) <= r2,
+ *   r2 = fl32(r * r) (squares are compared: one rounding fewer than sqrt(d2) <= r,
+ *   and exact on lattice inputs; the boundary is inclusive).  batch_y [n_y] int64
+ *   or NULL (graph 0); starts_x [G_x + 1]: graph g of y searches rows
+ *   [starts_x[g], starts_x[g + 1]) of x, a g outside [0, G_x) finds nothing.
+ *   One wave per query; hits go to a per-query slab of the workspace, their
+ *   counts are scanned, counts[0] = E (int64[4], device).  The caller reads E,
+ *   allocates out_y / out_x [E] and calls mp_radius_fill with the same workspace
+ *   (mp_radius_workspace(n_y, cap) bytes; n_y * cap < 2^31): the pairs sorted by
+ *   y, then x.
+ *
+ * mp_point_edge_features_f32: out[e, :F] = x_src[src[e], :] and
+ *   out[e, F + d] = pos_src[src[e], d] - pos_dst[dst[e], d], one pass; F = 0 (x_src
+ *   NULL) leaves the differences.  An edge whose src / dst lies outside
+ *   [0, n_src) / [0, n_dst) gets a row of zeros (the caller checks the ranges).
+ *
+ * Like the graclus entry points, the four calls above return int64_t, not a
+ * status: the launches enqueued, >= 0, or -(MP_ERR_* code) with the reason in
+ * mp_last_error() when the call is refused -- for a bad argument, before any
+ * launch.  They are not among the `int` status symbols a binding may wrap to
+ * raise: the caller tests the sign itself. */
+int64_t mp_fps_path(int64_t n_g);
+size_t mp_fps_workspace(int64_t n, int64_t max_n);
+int64_t mp_fps_f32(const float* pos, int64_t ldp, int64_t n, int32_t D, const int64_t* starts, int64_t n_graphs,
+               int64_t max_n, const int64_t* out_starts, const int64_t* start, int64_t* idx, size_t idx_bytes,
+               int64_t* counts, size_t counts_bytes, void* ws, size_t ws_bytes, void* stream);
+size_t mp_radius_workspace(int64_t n_y, int64_t cap);
+int64_t mp_radius_search_f32(const float* x, int64_t ldx, int64_t n_x, const float* y, int64_t ldy, int64_t n_y, int32_t D,
+                         const int64_t* batch_y, const int64_t* starts_x, int64_t n_graphs_x, float r, int64_t cap,
+                         int64_t* counts, size_t counts_bytes, void* ws, size_t ws_bytes, void* stream);
+int64_t mp_radius_fill(int64_t n_y, int64_t cap, int64_t n_edges, int64_t* out_y, int64_t* out_x, size_t out_bytes,
+                   void* ws, size_t ws_bytes, void* stream);
+int64_t mp_point_edge_features_f32(const float* x_src, int64_t ldx, int32_t F, const float* pos_src, int64_t ldps,
+                               int64_t n_src, const float* pos_dst, int64_t ldpd, int64_t n_dst, int32_t D,
+                               const int64_t* src, const int64_t* dst, int64_t n_edges, float* out, int64_t ldo,
+                               size_t out_bytes, void* stream);
+
 /* ---- other dtypes (csrc/mp_dtype.hip) -------------------------------------
  * torch_scatter 2.0.4 reduces any dtype ([U8/U9]); the fp32 hot path is
  * mp_aggregate_f32, these are the breadth path for the rest. */

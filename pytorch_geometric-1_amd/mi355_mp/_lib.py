@@ -194,6 +194,16 @@ SIGNATURES = {
     # these two return int64: a count >= 0, or -(code); the caller tests the sign (ops.graclus_match)
     "mp_graclus_init": (i64, [c_p, c_p, c_p, sz, i64, i64, u64, c_p, sz, c_p, sz, c_p, sz, c_p, sz, c_p]),
     "mp_graclus_rounds": (i64, [c_p, sz, c_p, sz, i64, i64, i64, i64, c_p, sz, c_p, sz, c_p, sz, c_p]),
+    "mp_fps_path": (i64, [i64]),                  # an answer (0, 1 or 2), not a status
+    "mp_fps_workspace": (sz, [i64, i64]),
+    # the four calls below return int64: launches >= 0, or -(code); the caller tests the sign (ops._count_call)
+    "mp_fps_f32": (i64, [c_p, i64, i64, i32, c_p, i64, i64, c_p, c_p, c_p, sz, c_p, sz, c_p, sz, c_p]),
+    "mp_radius_workspace": (sz, [i64, i64]),
+    "mp_radius_search_f32": (i64, [c_p, i64, i64, c_p, i64, i64, i32, c_p, c_p, i64, f32, i64, c_p, sz, c_p,
+                                            sz, c_p]),
+    "mp_radius_fill": (i64, [i64, i64, i64, c_p, c_p, sz, c_p, sz, c_p]),
+    "mp_point_edge_features_f32": (i64, [c_p, i64, i32, c_p, i64, i64, c_p, i64, i64, i32, c_p, c_p, i64, c_p,
+                                                  i64, sz, c_p]),
 }
 
 # Of the symbols declared `int` / `int32_t`, these answer a question (a version,

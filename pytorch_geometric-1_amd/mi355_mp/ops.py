@@ -2115,13 +2115,16 @@ class GraclusMatching(object):
         self.cluster, self.rounds, self.host_reads, self.launches = cluster, rounds, host_reads, launches
 
 
-def _graclus_call(nat, name, *args):
-    """The mp_graclus_* entry points return a count, or -(code): they are not
-    among the status symbols native() wraps, so the sign is tested here."""
+def _count_call(nat, name, *args):
+    """The mp_graclus_* and point-set entry points return a count, or -(code): they
+    are not among the status symbols native() wraps, so the sign is tested here."""
     rc = getattr(nat, name)(*args)
     if rc < 0:
         raise RuntimeError("%s failed (code %d): %s" % (name, -rc, nat.mp_last_error().decode(errors="replace")))
     return rc
+
+
+_graclus_call = _count_call
 
 
 def graclus_incidence(edge_index, n):
@@ -2200,3 +2203,202 @@ def graclus_match(edge_index, weight, n, seed=0, rounds_per_read=None):
         if got[1 + ((first - 1) & 1)] == 0:
             break
     return GraclusMatching(cluster, rounds, reads, launches)
+
+
+# ---------------------------------------------------------------------------
+# Point sets (PyG 1.4.3 nn.fps / nn.radius / nn.conv.PointConv [U]; csrc/mp_point.hip)
+# ---------------------------------------------------------------------------
+
+POINT_MAX_D = 8
+_F32_MAX = 3.4028234663852886e38
+
+
+def fps_path(n_g):
+    """0 = one wave, 1 = one workgroup with the points in registers, 2 = one
+    workgroup with m in the workspace: how mp_fps_f32 samples a graph of n_g
+    points (mp_fps_path; needs no GPU)."""
+    return int(_lib.native().mp_fps_path(int(n_g)))
+
+
+def _point_rows(pos, what):
+    """[n, D] float32 rows of a point tensor (1 <= D <= 8; a row stride is kept)."""
+    if pos.dtype != torch.float32:
+        raise TypeError("mi355_mp: %s must be float32 (got %s)" % (what, pos.dtype))
+    pos = pos.view(-1, 1) if pos.dim() == 1 else pos
+    if pos.dim() != 2:
+        raise ValueError("mi355_mp: %s must be [N] or [N, D]" % what)
+    if not 1 <= pos.shape[1] <= POINT_MAX_D:
+        raise ValueError("mi355_mp: %s takes 1 to %d columns (got %d)" % (what, POINT_MAX_D, pos.shape[1]))
+    if pos.stride(1) != 1 or pos.stride(0) < pos.shape[1]:
+        pos = pos.contiguous()
+    return pos
+
+
+def _sorted_layout(batch, n, device, what):
+    layout = cached_batch_layout(batch, n, device)
+    if layout.unsorted:
+        raise ValueError("mi355_mp: %s must be sorted (it descends %d times)" % (what, layout.unsorted))
+    note_num_graphs(batch, layout.n_graphs)
+    return layout
+
+
+def fps(pos, batch=None, ratio=0.5, start=None):
+    """Farthest point sampling (mp_fps_f32): idx int64 [K], grouped by graph in
+    ascending order, within a graph in selection order; graph g keeps
+    ceil(fl32(ratio * fl32(n_g))) points (the TopKPooling count).
+
+    pos: float32 [n, D], D <= 8; batch: sorted int64 [n] or None; start: None
+    (every graph starts at its first point) or a device int64 [G] of in-graph
+    offsets.  A pure function of its arguments.  ValueError for an unsorted
+    batch, D > 8 or a start outside [0, n_g).  One device-to-host read (K and
+    the rejected starts), beyond the cached batch layout."""
+    _lib.require_device(pos, batch, start)
+    nat = _lib.native()
+    ratio = check_ratio(ratio)
+    pos = _point_rows(pos.detach(), "pos")
+    n, D = pos.shape
+    dev = pos.device
+    layout = _sorted_layout(batch, n, dev, "batch")
+    G = layout.n_graphs
+    if start is not None:
+        if start.dtype != torch.int64 or start.dim() != 1 or start.shape[0] != G:
+            raise ValueError("mi355_mp: start must be int64 [%d] (got %s %s)" % (G, start.dtype, tuple(start.shape)))
+        start = start.contiguous()
+    out_starts, counts = topk_counts(layout.starts, ratio, layout.max_n)
+    idx = torch.empty(n, dtype=torch.int64, device=dev)
+    wsb = nat.mp_fps_workspace(n, layout.max_n)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    _count_call(nat, "mp_fps_f32", _lib.ptr(pos if n else None), pos.stride(0), n, D, layout.starts.data_ptr(), G,
+                layout.max_n, out_starts.data_ptr(), _lib.ptr(start), _lib.ptr(idx if n else None), _lib.nbytes(idx),
+                counts.data_ptr(), _lib.nbytes(counts), ws.data_ptr(), wsb, _lib.stream_ptr(dev))
+    K, bad = counts[:2].tolist()
+    if bad:
+        raise ValueError("fps: %d graphs have a start offset outside [0, n_g)" % bad)
+    return idx[:K]
+
+
+def fps_random_start(layout, generator=None):
+    """start [G] for fps: floor(u * n_g) clamped to n_g - 1, u uniform on [0, 1)
+    from torch's device generator.  No host read."""
+    starts = layout.starts
+    n_g = starts[1:] - starts[:-1]
+    u = torch.rand(layout.n_graphs, device=starts.device, generator=generator)
+    s = (u * n_g.to(torch.float32)).floor().to(torch.int64)
+    return torch.minimum(s, n_g - 1).clamp_(min=0)
+
+
+def radius_search(x, y, r, batch_x=None, batch_y=None, max_num_neighbors=32):
+    """The fixed-radius neighbour search (mp_radius_search_f32 + mp_radius_fill):
+    int64 [2, E], row 0 indices into y, row 1 into x, sorted by y then x; for every
+    y the first max_num_neighbors points of x, in ascending index, of the same
+    graph with d2(x_i, y) <= fl32(fl32(r) * fl32(r)).
+
+    x [n_x, D], y [n_y, D] float32 (D <= 8); batch_x / batch_y: sorted int64 or
+    both None.  ValueError for an unsorted batch, r negative or not finite,
+    max_num_neighbors < 1, other widths.  One device-to-host read (E), beyond
+    the cached batch layouts."""
+    _lib.require_device(x, y, batch_x, batch_y)
+    nat = _lib.native()
+    r = float(r)
+    if not (0.0 <= r <= _F32_MAX):
+        raise ValueError("radius: r must be finite and not negative (got %r)" % (r,))
+    cap = int(max_num_neighbors)
+    if cap < 1:
+        raise ValueError("radius: max_num_neighbors must be at least 1 (got %d)" % cap)
+    if (batch_x is None) != (batch_y is None):
+        raise ValueError("radius: batch_x and batch_y come together or not at all")
+    x = _point_rows(x.detach(), "x")
+    y = _point_rows(y.detach(), "y")
+    if x.shape[1] != y.shape[1]:
+        raise ValueError("radius: x has %d columns, y %d" % (x.shape[1], y.shape[1]))
+    (n_x, D), n_y = x.shape, y.shape[0]
+    dev = x.device
+    lx = _sorted_layout(batch_x, n_x, dev, "batch_x")
+    _sorted_layout(batch_y, n_y, dev, "batch_y")
+    cap = min(cap, max(lx.max_n, 1))          # a query never finds more than its graph holds
+    if n_y and cap >= (1 << 31) // n_y:
+        raise ValueError("radius: n_y * max_num_neighbors = %d * %d is not below 2^31" % (n_y, cap))
+    if batch_y is not None:
+        batch_y = batch_y.contiguous()
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    wsb = nat.mp_radius_workspace(n_y, cap)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    st = _lib.stream_ptr(dev)
+    _count_call(nat, "mp_radius_search_f32", _lib.ptr(x if n_x else None), x.stride(0), n_x,
+                _lib.ptr(y if n_y else None), y.stride(0), n_y, D, _lib.ptr(batch_y), lx.starts.data_ptr(), lx.n_graphs, r, cap, counts.data_ptr(),
+                _lib.nbytes(counts), ws.data_ptr(), wsb, st)
+    E = int(counts[0].item())
+    out = torch.empty((2, E), dtype=torch.int64, device=dev)
+    _count_call(nat, "mp_radius_fill", n_y, cap, E, _lib.ptr(out[0] if E else None), _lib.ptr(out[1] if E else None),
+                E * 8, ws.data_ptr(), wsb, st)
+    return out
+
+
+class _PointEdgeFeatures(torch.autograd.Function):
+    """[x_src[src] | pos_src[src] - pos_dst[dst]] in one pass
+    (mp_point_edge_features_f32).  Backward: the row gather's backward by source
+    for x_src and pos_src, the negated segment sum by destination for pos_dst --
+    the engine's deterministic sums over the cached CSR of each index."""
+
+    @staticmethod
+    def forward(ctx, x_src, pos_src, pos_dst, src, dst):
+        nat = _lib.native()
+        F = 0 if x_src is None else x_src.shape[1]
+        D = pos_src.shape[1]
+        E = src.numel()
+        dev = pos_src.device
+        out = torch.empty((E, F + D), dtype=torch.float32, device=dev)
+        _count_call(nat, "mp_point_edge_features_f32", _lib.ptr(x_src), 0 if x_src is None else x_src.stride(0), F,
+                    pos_src.data_ptr(), pos_src.stride(0), pos_src.shape[0], pos_dst.data_ptr(), pos_dst.stride(0),
+                    pos_dst.shape[0], D, src.data_ptr(), dst.data_ptr(), E, out.data_ptr(), F + D, _lib.nbytes(out),
+                    _lib.stream_ptr(dev))
+        ctx.F, ctx.n_src, ctx.n_dst = F, pos_src.shape[0], pos_dst.shape[0]
+        ctx.save_for_backward(src, dst)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        src, dst = ctx.saved_tensors
+        F = ctx.F
+        g = g.contiguous()
+        need_x = F > 0 and ctx.needs_input_grad[0]
+        g_x = g_ps = g_pd = None
+        if need_x or ctx.needs_input_grad[1]:
+            by_src = csr_for_index(src, ctx.n_src)
+            if need_x:
+                g_x, _ = _aggregate(by_src, "eid", g[:, :F], None, "sum", 0, None)
+            if ctx.needs_input_grad[1]:
+                g_ps, _ = _aggregate(by_src, "eid", g[:, F:], None, "sum", 0, None)
+        if ctx.needs_input_grad[2]:
+            g_pd, _ = _aggregate(csr_for_index(dst, ctx.n_dst), "eid", g[:, F:], None, "sum", 0, None)
+            g_pd = g_pd.neg_()
+        return g_x, g_ps, g_pd, None, None
+
+
+def point_edge_features(x_src, pos_src, pos_dst, src, dst):
+    """PointConv's per-edge matrix [E, F + D]: out[e, :F] = x_src[src[e]] and
+    out[e, F:] = pos_src[src[e]] - pos_dst[dst[e]]; x_src None means F = 0.
+    Differentiable in x_src, pos_src and pos_dst; edges in any order.  An index
+    outside its range raises IndexError (check_row_index: cached per index)."""
+    _lib.require_device(x_src, pos_src, pos_dst, src, dst)
+    pos_src = _point_rows(pos_src, "pos_src")
+    pos_dst = _point_rows(pos_dst, "pos_dst")
+    if pos_src.shape[1] != pos_dst.shape[1]:
+        raise ValueError("mi355_mp: pos_src has %d columns, pos_dst %d" % (pos_src.shape[1], pos_dst.shape[1]))
+    if x_src is not None:
+        x_src = _f32_2d(x_src, "x_src")
+        if x_src.shape[0] != pos_src.shape[0]:
+            raise ValueError("mi355_mp: x_src has %d rows, pos_src %d" % (x_src.shape[0], pos_src.shape[0]))
+        if x_src.shape[1] == 0:
+            x_src = None
+        elif x_src.stride(0) < x_src.shape[1]:
+            x_src = x_src.contiguous()
+    if src.dtype != torch.int64 or dst.dtype != torch.int64 or src.dim() != 1 or src.shape != dst.shape:
+        raise ValueError("mi355_mp: src and dst must be int64 vectors of one length")
+    if src.stride(0) != 1:
+        src = src.contiguous()
+    if dst.stride(0) != 1:
+        dst = dst.contiguous()
+    check_row_index(src, pos_src.shape[0], "point_edge_features")
+    check_row_index(dst, pos_dst.shape[0], "point_edge_features")
+    return _PointEdgeFeatures.apply(x_src, pos_src, pos_dst, src, dst)

@@ -8,6 +8,7 @@ from .agnn_conv import AGNNConv
 from .sg_conv import SGConv
 from .gin_conv import GINConv
 from .spline_conv import SplineConv
+from .point_conv import PointConv
 
 __all__ = ["MessagePassing", "GCNConv", "GATConv", "SAGEConv", "GraphConv", "ChebConv", "AGNNConv", "SGConv", "GINConv",
-           "SplineConv"]
+           "SplineConv", "PointConv"]

@@ -1,5 +1,6 @@
 """Graph pooling (PyG 1.4.3 nn.pool): TopKPooling and the cluster pools
-(voxel_grid, graclus, max_pool, avg_pool) on the native engine."""
+(voxel_grid, graclus, max_pool, avg_pool) and the point-set samplers (fps, radius,
+radius_graph) on the native engine."""
 from .topk_pool import TopKPooling, filter_adj, topk
 from .voxel_grid import voxel_grid
 from .graclus import graclus
@@ -7,6 +8,8 @@ from .consecutive import consecutive_cluster
 from .pool import pool_edge, pool_batch, pool_pos
 from .max_pool import max_pool, max_pool_x
 from .avg_pool import avg_pool, avg_pool_x
+from .fps import fps
+from .radius import radius, radius_graph
 
 __all__ = ["TopKPooling", "topk", "filter_adj", "voxel_grid", "consecutive_cluster", "pool_edge", "pool_batch",
-           "pool_pos", "max_pool", "max_pool_x", "avg_pool", "avg_pool_x", "graclus"]
+           "pool_pos", "max_pool", "max_pool_x", "avg_pool", "avg_pool_x", "graclus", "fps", "radius", "radius_graph"]
