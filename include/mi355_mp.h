@@ -669,6 +669,60 @@ int mp_spline_aggregate_gather_f32(const mp_csr* g, const float* pseudo, int64_t
                                    const float* x, int64_t ldx, int32_t F, const float* row_scale,
                                    const float* bias, float* out, int64_t ldo, void* stream);
 
+/* ---- NNConv: factored edge-conditioned aggregation (csrc/mp_nnconv.hip) -----
+ * For an edge network that ends in a Linear (the head: weight [Cin*Cout, H],
+ * bias [Cin*Cout]) the per-edge weight matrices W_e = reshape(head(h_e), [Cin,
+ * Cout]) of PyG 1.4.3's nn.conv.NNConv [U] are never built.  With h_e in R^H the
+ * head's input, ht_e = [h_e, 1] and L[(h, c), o] = head.weight[c*Cout + o, h]
+ * (row block h = H: head.bias):
+ *   sum_{e -> i} x_j W_e = (sum_{e -> i} ht_e (x) x_j) L
+ * one segmented pass and one dense node-level GEMM (the caller's), in place of
+ * an [E, Cin*Cout] array and E mat-vecs.
+ * h is [n_h_edges, ldh >= H] fp32 in ORIGINAL edge order, read through g->eid;
+ * n_h_edges must cover the edge-id space of g (g->n_ids, or g->n_edges when
+ * that is 0).  The trailing 1 of ht is implicit: no concatenated copy is taken.
+ * Limits (mp_nnconv_ok != 0): H >= 1, Cin >= 1, Cout >= 1 and (H + 1) * Cin,
+ * (H + 1) * Cout <= 2^20 floats (one row of Z or Y, 4 MiB).  A row's
+ * accumulators are held in registers and tiled over the grid, so neither LDS
+ * nor the register file bounds a shape; the limit keeps every in-row offset and
+ * grid dimension in range.  The aggregate calls apply it to their own (H, Cin)
+ * or (H, F).
+ * Both aggregate calls walk g->rowptr / col / eid only (col and eid required;
+ * the wave schedule is not read), one owner per output entry visits its row's
+ * slots in slot order and adds left to right (gather: h = 0..H inside a slot):
+ * fp32, deterministic, no atomics.  Rows of any length are summed serially;
+ * hub rows are not split.  Every output entry of every row is written exactly
+ * once (zeros for rows without slots); padding beyond it is left untouched.
+ *   mp_nnconv_aggregate_bins_f32 (x [n_cols, ldx >= Cin]):
+ *     out[r, h*Cin + c] = scale[r] * sum_{slots of r} ht[eid[slot]][h] * x[col[slot], c]
+ *     ldo >= (H + 1) * Cin.  Lanes run over the flattened (h, c) for Cin < 32
+ *     (several rows share a wave when (H + 1) * Cin < 64), over c with 16
+ *     values of h per lane from Cin = 32 on (ht wave-uniform per slot).
+ *   mp_nnconv_aggregate_gather_f32 (y [n_cols, H + 1, F], ldy >= (H + 1) * F):
+ *     out[r, f] = scale[r] * sum_{slots of r} sum_h ht[eid[slot]][h] * y[col[slot], h*F + f] (+ bias[f])
+ *     ldo >= F.  Lanes run over f.
+ *   mp_nnconv_edge_grad_f32 (rows / cols [n_edges] int64: each edge's row of dz
+ *     and of x, the caller has range-checked them; dz [.., lddz >= (H+1)*Cin]):
+ *     dh[e, h] = sum_c dz[rows[e], h*Cin + c] * x[cols[e], c]  for h < H
+ *     edge-parallel, nothing is reduced across edges; written in edge order,
+ *     lddh >= H, dh_bytes: the extent of dh, at least ((n_edges - 1) * lddh + H)
+ *     floats, checked before any launch.
+ * row_scale [n_rows] or NULL (= 1), bias [F] or NULL.
+ * Like the graclus and point-set entry points these are additions to ABI 7 that
+ * return int64_t, not a status: the launches enqueued, >= 0, or -(MP_ERR_* code)
+ * with the reason in mp_last_error() when the call is refused -- for a bad
+ * argument (-MP_ERR_ARG), before any launch.  The caller tests the sign. */
+int64_t mp_nnconv_ok(int32_t H, int32_t Cin, int32_t Cout);
+int64_t mp_nnconv_aggregate_bins_f32(const mp_csr* g, const float* h, int64_t n_h_edges, int64_t ldh, int32_t H,
+                                     const float* x, int64_t ldx, int32_t Cin, const float* row_scale, float* out,
+                                     int64_t ldo, void* stream);
+int64_t mp_nnconv_aggregate_gather_f32(const mp_csr* g, const float* h, int64_t n_h_edges, int64_t ldh, int32_t H,
+                                       const float* y, int64_t ldy, int32_t F, const float* row_scale,
+                                       const float* bias, float* out, int64_t ldo, void* stream);
+int64_t mp_nnconv_edge_grad_f32(const int64_t* rows, const int64_t* cols, int64_t n_edges, const float* dz,
+                                int64_t lddz, const float* x, int64_t ldx, int32_t H, int32_t Cin, float* dh,
+                                int64_t lddh, size_t dh_bytes, void* stream);
+
 /* ---- TopKPooling: score, per-graph select, gate, filter_adj (csrc/mp_pool.hip)
  * PyG 1.4.3 nn.pool.topk_pool [U] as one deterministic native path: no atomics
  * on values (two integer counters and one integer maximum aside), no dense

@@ -204,6 +204,13 @@ SIGNATURES = {
     "mp_radius_fill": (i64, [i64, i64, i64, c_p, c_p, sz, c_p, sz, c_p]),
     "mp_point_edge_features_f32": (i64, [c_p, i64, i32, c_p, i64, i64, c_p, i64, i64, i32, c_p, c_p, i64, c_p,
                                                   i64, sz, c_p]),
+    # NNConv (csrc/mp_nnconv.hip): int64 returns like the two groups above, the sign tested by ops._count_call
+    "mp_nnconv_ok": (i64, [i32, i32, i32]),        # an answer (0 or 1), not a status
+    "mp_nnconv_aggregate_bins_f32": (i64, [ctypes.POINTER(MpCsr), c_p, i64, i64, i32, c_p, i64, i32, c_p, c_p, i64,
+                                           c_p]),
+    "mp_nnconv_aggregate_gather_f32": (i64, [ctypes.POINTER(MpCsr), c_p, i64, i64, i32, c_p, i64, i32, c_p, c_p, c_p,
+                                             i64, c_p]),
+    "mp_nnconv_edge_grad_f32": (i64, [c_p, c_p, i64, c_p, i64, c_p, i64, i32, i32, c_p, i64, sz, c_p]),
 }
 
 # Of the symbols declared `int` / `int32_t`, these answer a question (a version,

@@ -1468,6 +1468,207 @@ def spline_propagate(graph, x, weight, pseudo, kernel_size, is_open_spline, degr
 
 
 # ---------------------------------------------------------------------------
+# NNConv: factored edge-conditioned aggregation (csrc/mp_nnconv.hip)
+# ---------------------------------------------------------------------------
+
+def nnconv_ok(H, c_in, c_out):
+    """Whether (H, Cin, Cout) lies inside the fused path's limits (mp_nnconv_ok)."""
+    return bool(_lib.native().mp_nnconv_ok(int(H), int(c_in), int(c_out)))
+
+
+def _nnconv_rows(t, what):
+    t = _f32_2d(t, what)
+    return t if t.stride(0) >= max(t.shape[1], 1) else t.contiguous()
+
+
+def nnconv_bins(csr, h, x, row_scale=None, out=None):
+    """Z[r, k*Cin + c] = scale[r] * sum over the slots of r of ht[eid[slot]][k] *
+    x[col[slot], c], ht = [h, 1] (mp_nnconv_aggregate_bins_f32); h [E, H] in edge
+    order.  out: a [n_rows, >= (H+1)*Cin] tensor to write into.  No autograd."""
+    nat = _lib.native()
+    h, x = _nnconv_rows(h, "h"), _nnconv_rows(x, "x")
+    H, c_in = h.shape[1], x.shape[1]
+    if out is None:
+        out = torch.empty((csr.n_rows, (H + 1) * c_in), dtype=torch.float32, device=x.device)
+    if csr.n_rows:
+        _count_call(nat, "mp_nnconv_aggregate_bins_f32", csr.struct("other"), h.data_ptr(), h.shape[0], h.stride(0), H,
+                    x.data_ptr(), x.stride(0), c_in, _lib.ptr(row_scale), out.data_ptr(), out.stride(0),
+                    _lib.stream_ptr(x.device))
+    return out
+
+
+def nnconv_gather(csr, h, y, F, row_scale=None, bias=None, out=None):
+    """out[r, f] = scale[r] * sum over the slots of r and k <= H of ht[eid[slot]][k]
+    * y[col[slot], k*F + f] (+ bias) (mp_nnconv_aggregate_gather_f32); y [n_cols,
+    (H+1)*F].  No autograd."""
+    nat = _lib.native()
+    h, y = _nnconv_rows(h, "h"), _nnconv_rows(y, "y")
+    H, F = h.shape[1], int(F)
+    if out is None:
+        out = torch.empty((csr.n_rows, F), dtype=torch.float32, device=y.device)
+    if csr.n_rows:
+        _count_call(nat, "mp_nnconv_aggregate_gather_f32", csr.struct("other"), h.data_ptr(), h.shape[0], h.stride(0),
+                    H, y.data_ptr(), y.stride(0), F, _lib.ptr(row_scale), _lib.ptr(bias), out.data_ptr(),
+                    out.stride(0), _lib.stream_ptr(y.device))
+    return out
+
+
+def nnconv_edge_grad(rows, cols, dz, x, H):
+    """dh[e, k] = sum_c dz[rows[e], k*Cin + c] * x[cols[e], c] for k < H
+    (mp_nnconv_edge_grad_f32); rows / cols int64 [E], range-checked by the
+    caller (a CSR built from them has done it).  No autograd."""
+    nat = _lib.native()
+    dz, x = _nnconv_rows(dz, "dz"), _nnconv_rows(x, "x")
+    rows, cols = rows.contiguous(), cols.contiguous()
+    E, H = rows.numel(), int(H)
+    dh = torch.empty((E, H), dtype=torch.float32, device=x.device)
+    if E:
+        _count_call(nat, "mp_nnconv_edge_grad_f32", rows.data_ptr(), cols.data_ptr(), E, dz.data_ptr(), dz.stride(0),
+                    x.data_ptr(), x.stride(0), H, x.shape[1], dh.data_ptr(), dh.stride(0), _lib.nbytes(dh),
+                    _lib.stream_ptr(x.device))
+    return dh
+
+
+def nnconv_form(H, c_in, c_out, E, N):
+    """The forward's form, by the floats each form moves (a pure function of the
+    shape; measured in tools/bench_nnconv.py):
+      bins    reads H + Cin floats per edge, writes Z [N, (H+1) Cin] and reads it
+              back in the GEMM:            E (H + Cin)            + 2 N (H+1) Cin
+      gather  writes Y [N, (H+1) Cout] in the GEMM and gathers H + (H+1) Cout
+              floats per edge:             E (H + (H+1) Cout)     +   N (H+1) Cout
+    The lower count wins, ties to bins (it keeps Z for the head's gradient, the
+    gather form recomputes it in the backward).  Gather is ahead only where Cout
+    is far below Cin and the graph is sparse: E (H+1) Cout < N (H+1) (2 Cin -
+    Cout) + E Cin.  Every measured shape is ahead of the per-edge recipe in the
+    form picked here, so none is sent to the generic path."""
+    bins = E * (H + c_in) + 2 * N * (H + 1) * c_in
+    gather = E * (H + (H + 1) * c_out) + N * (H + 1) * c_out
+    return "bins" if bins <= gather else "gather"
+
+
+def _nnconv_head_matrix(head_weight, head_bias, c_in, c_out):
+    """L [(H+1) Cin, Cout] (H Cin rows without a head bias): L[k*Cin + c, o] =
+    head_weight[c*Cout + o, k], rows k = H the head bias -- one permuting copy."""
+    H = head_weight.shape[1]
+    rows = H + (0 if head_bias is None else 1)
+    L = torch.empty((rows * c_in, c_out), dtype=torch.float32, device=head_weight.device)
+    L[:H * c_in].view(H, c_in, c_out).copy_(head_weight.reshape(c_in, c_out, H).permute(2, 0, 1))
+    if head_bias is not None:
+        L[H * c_in:].copy_(head_bias.reshape(c_in, c_out))
+    return L
+
+
+class _NNConvPropagate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, h, head_weight, head_bias, bias, graph, reduce, form):
+        H, c_in = h.shape[1], x.shape[1]
+        c_out = head_weight.shape[0] // c_in
+        csr = graph.dst
+        has_hb = head_bias is not None
+        used = (H + 1 if has_hb else H)                  # row blocks of L: without a head bias the last is zero
+        scale = None
+        if reduce == "mean":
+            scale = (1.0 / csr.degree().clamp(min=1).to(torch.float32)).contiguous()
+        L = _nnconv_head_matrix(head_weight, head_bias, c_in, c_out)
+        Z = None
+        if form == "bins":
+            Z = nnconv_bins(csr, h, x, scale)
+            Zu = Z[:, :used * c_in]
+            out = torch.mm(Zu, L) if bias is None else torch.addmm(bias, Zu, L)
+        else:
+            Lp = L.view(used, c_in, c_out).permute(1, 0, 2).reshape(c_in, used * c_out)
+            if has_hb:
+                Y = torch.mm(x, Lp)
+            else:                                        # the kernel reads H + 1 blocks: the last one is zero
+                Y = torch.empty((x.shape[0], (H + 1) * c_out), dtype=torch.float32, device=x.device)
+                Y[:, :H * c_out] = torch.mm(x, Lp)
+                Y[:, H * c_out:].zero_()
+            out = nnconv_gather(csr, h, Y, c_out, scale, bias)
+        ctx.graph, ctx.has_bias, ctx.has_hb = graph, bias is not None, has_hb
+        want_head = ctx.needs_input_grad[2] or (has_hb and ctx.needs_input_grad[3])
+        # the cached Graph holds its edge_index weakly and builds the transposed CSR
+        # on first use, in backward: keep the tensor alive until then
+        ctx.save_for_backward(x, h, L, scale, Z if want_head else None, graph._edge_index())
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, h, L, scale, Z, edge_index = ctx.saved_tensors
+        graph, has_hb = ctx.graph, ctx.has_hb
+        H, c_in, c_out = h.shape[1], x.shape[1], L.shape[1]
+        used = H + 1 if has_hb else H
+        g = g.contiguous()
+        gx = gh = gw = ghb = gb = None
+        if ctx.has_bias and ctx.needs_input_grad[4]:
+            gb = col_sums(g)
+        want_x, want_h = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        want_head = ctx.needs_input_grad[2] or (has_hb and ctx.needs_input_grad[3])
+        if want_head:
+            if Z is None:                                # the gather form never built it
+                Z = nnconv_bins(graph.dst, h, x, scale)
+            gL = torch.mm(Z[:, :used * c_in].t(), g)     # Z carries the row scale
+            if ctx.needs_input_grad[2]:
+                gw = gL[:H * c_in].view(H, c_in, c_out).permute(1, 2, 0).reshape(c_in * c_out, H)
+            if has_hb and ctx.needs_input_grad[3]:
+                ghb = gL[H * c_in:].reshape(c_in * c_out)
+        if want_x or want_h:
+            gs = g if scale is None else g * scale.view(-1, 1)
+            if has_hb:
+                dZ = torch.mm(gs, L.t())
+            else:
+                dZ = torch.empty((g.shape[0], (H + 1) * c_in), dtype=torch.float32, device=g.device)
+                dZ[:, :H * c_in] = torch.mm(gs, L.t())
+                dZ[:, H * c_in:].zero_()
+            if want_x:
+                # the transposed pass: rows = source nodes, gathers destination rows of dZ
+                gx = nnconv_gather(graph.src, h, dZ, c_in)
+            if want_h:
+                gh = nnconv_edge_grad(edge_index[graph.i], edge_index[graph.j], dZ, x, H)
+        return gx, gh, gw, ghb, gb, None, None, None
+
+
+def nnconv_propagate(graph, x, h, head_weight, head_bias, reduce, form=None, bias=None):
+    """out[i] = AGGR_{e = (j -> i)} x[j] @ reshape(head_weight @ h[e] + head_bias, [Cin, Cout]) (+ bias)
+
+    NNConv's propagate for an edge network ending in a Linear (the head), with
+    no per-edge weight matrix: one segmented pass and one node-level GEMM.  h
+    [E, H] is the head's input in edge order, head_weight [Cin*Cout, H],
+    head_bias [Cin*Cout] or None (then the bias row block of L does not exist).
+    reduce 'add' or 'mean' (mean divides by max(deg, 1)); form None picks by
+    nnconv_form, 'bins' / 'gather' force one.  Deterministic, native forward and
+    backward: d x by the gather kernel over the transposed CSR, d h by the
+    edge-grad kernel (skipped when h needs no gradient), d head by Z^T g with Z
+    saved by the bins form and recomputed after the gather form."""
+    if reduce == "max":
+        raise NotImplementedError("mi355_mp: nnconv_propagate has no aggr='max' (add and mean only)")
+    if reduce not in ("add", "sum", "mean"):
+        raise ValueError("unknown reduce %r" % (reduce,))
+    if form not in (None, "bins", "gather"):
+        raise ValueError("unknown form %r" % (form,))
+    _lib.require_device(x, h, head_weight, head_bias, bias)
+    x, h = _nnconv_rows(x, "x"), _nnconv_rows(h, "h")
+    H, c_in = h.shape[1], x.shape[1]
+    if head_weight.dtype != torch.float32 or head_weight.dim() != 2 or head_weight.shape[1] != H \
+            or c_in == 0 or head_weight.shape[0] % max(c_in, 1):
+        raise ValueError("mi355_mp: head_weight must be float32 [%d * Cout, %d] (got %s %s)"
+                         % (c_in, H, head_weight.dtype, tuple(head_weight.shape)))
+    c_out = head_weight.shape[0] // c_in
+    if head_bias is not None and tuple(head_bias.shape) != (c_in * c_out,):
+        raise ValueError("mi355_mp: head_bias must be [%d] (got %s)" % (c_in * c_out, tuple(head_bias.shape)))
+    if not nnconv_ok(H, c_in, c_out):
+        raise NotImplementedError("mi355_mp: outside the fused NNConv path's limits: "
+                                  + _lib.native().mp_last_error().decode(errors="replace"))
+    if h.shape[0] != graph.dst.n_edges:
+        raise ValueError("mi355_mp: h has %d rows, the graph %d edges" % (h.shape[0], graph.dst.n_edges))
+    if x.shape[0] != graph.n_src:
+        raise ValueError("mi355_mp: x has %d rows, the graph %d source nodes" % (x.shape[0], graph.n_src))
+    if form is None:
+        form = nnconv_form(H, c_in, c_out, h.shape[0], x.shape[0])
+    reduce = "add" if reduce == "sum" else reduce
+    return _NNConvPropagate.apply(x, h, head_weight, head_bias, bias, graph, reduce, form)
+
+
+# ---------------------------------------------------------------------------
 # TopKPooling (PyG 1.4.3 nn.pool.topk_pool [U]; csrc/mp_pool.hip)
 # ---------------------------------------------------------------------------
 

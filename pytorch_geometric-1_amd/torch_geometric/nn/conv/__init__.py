@@ -9,6 +9,7 @@ from .sg_conv import SGConv
 from .gin_conv import GINConv
 from .spline_conv import SplineConv
 from .point_conv import PointConv
+from .nn_conv import NNConv
 
 __all__ = ["MessagePassing", "GCNConv", "GATConv", "SAGEConv", "GraphConv", "ChebConv", "AGNNConv", "SGConv", "GINConv",
-           "SplineConv", "PointConv"]
+           "SplineConv", "PointConv", "NNConv"]
