@@ -723,6 +723,80 @@ int64_t mp_nnconv_edge_grad_f32(const int64_t* rows, const int64_t* cols, int64_
                                 int64_t lddz, const float* x, int64_t ldx, int32_t H, int32_t Cin, float* dh,
                                 int64_t lddh, size_t dh_bytes, void* stream);
 
+/* ---- Attention readout: Set2Set / GlobalAttention (csrc/mp_glob.hip) ---------
+ * PyG 1.4.3's nn.glob.Set2Set and nn.glob.GlobalAttention [U] share one step: a
+ * softmax of one scalar per node over each graph, then the softmax-weighted sum
+ * of the graph's node rows.  Here it is one pass over x per graph, forward and
+ * backward; nothing of size N is written but e.  All arithmetic is fp32.
+ * Graphs are segment starts: starts [n_graphs + 1] int64 on the device, non-
+ * decreasing, within [0, n] (ops.cached_batch_layout of a sorted batch vector);
+ * g(i) is the graph of node i.  max_n: at least the node count of the largest
+ * graph (it sizes grids and the workspace, never a result).
+ * Forward, x [n, ldx >= C] and exactly one of
+ *   q [n_graphs, ldq >= C]   query mode:  e_i = sum_c x[i, c] * q[g(i), c]
+ *   score [n]                score mode:  e_i = score[i]
+ * gives per graph g
+ *   m_g = max_i e_i,  den_g = sum_i exp(e_i - m_g),  a_i = exp(e_i - m_g) / den_g
+ *   out[g, c] = sum_i a_i * x[i, c]            out [n_graphs, ldo >= C]
+ * and writes e [n] and stats [n_graphs, 2] = (m, den) for the backward; alpha
+ * [n] = a is written when it is not NULL (one more launch).  q_out, when not
+ * NULL (query mode only), receives q[g, :] at q_out[g * ldo + c]: with out =
+ * base + C and q_out = base, ldo = 2C, Set2Set's q_star = [q | r] is written
+ * without a concatenation.
+ * Upstream divides by den + 1e-16.  A graph with a node has den >= 1, and in
+ * fp32 1 + 1e-16 == 1 (so den + 1e-16 == den bit for bit): the kernels divide
+ * by den.  A graph without nodes (anywhere, trailing graphs included) gets
+ * out[g, :] = 0 and stats = (0, 0), upstream's result (scatter_max and
+ * scatter_add fill 0).  Every entry of out (and q_out), stats, e (and alpha) is
+ * written exactly once; padding beyond C is left untouched; nothing needs a
+ * memset.  Only finite inputs are specified.
+ * Backward, given dr [n_graphs, lddr >= C], the forward's e, stats and r = out
+ * (ldr its row stride):
+ *   s_g = sum_c dr[g, c] * r[g, c]
+ *   de_i = a_i * (sum_c dr[g(i), c] * x[i, c] - s_g)
+ *   query mode:  dx[i, :] = a_i * dr[g(i), :] + de_i * q[g(i), :],  dq[g, :] = sum_i de_i * x[i, :]
+ *   score mode:  dx[i, :] = a_i * dr[g(i), :],                      dscore[i] = de_i
+ * one pass over x; a is recomputed from e and stats.  q NULL selects score
+ * mode.  dx, dq and dscore may each be NULL (not computed); dq needs q, dscore
+ * needs q == NULL.  Rows of dq of graphs without nodes are zero.
+ * Paths, chosen per graph from (n_g, C) alone -- mp_readout_path (needs no GPU):
+ *   0  one wave per graph, four graphs per workgroup
+ *   1  one workgroup per graph, wave partials merged through LDS in wave order
+ *   2  the graph cut into chunks of mp_readout_chunk(C) nodes, a workgroup each;
+ *      chunk partials (m, den, r[C]) go to the workspace and a second kernel
+ *      merges them in chunk order, rescaled by exp(m_chunk - m_g) (dq: summed)
+ * No atomics, every merge order fixed: a graph's out, stats, dx and dq are the
+ * same bits run to run and whether the graph is batched alone or among others
+ * (given the same C, strides and 16-byte alignment of the row pointers, which
+ * select 16-byte or scalar loads and with them the order of the dot's terms).
+ * C >= 1 is any width; lanes run over channels, rows wider than a pass are tiled
+ * over the grid.  Limits, checked before any launch (a refused call writes
+ * nothing): n_graphs < 2^31, max_n <= 65535 * mp_readout_chunk(C), and no launch
+ * of 2^24 workgroups or more: n_graphs * ceil(max_n / mp_readout_chunk(C)) *
+ * channel tiles < 2^24 when the largest graph is split (one very large graph
+ * beside very many others; the grid is sized from max_n alone).
+ * ws: mp_readout_workspace(n, n_graphs, max_n, C) bytes, required (not NULL)
+ * by both calls, one layout (csrc/mp_glob.hip ReadoutWs); every caller-sized
+ * array travels with its extent in bytes, checked before any launch.
+ * Additions to ABI 7 that return int64_t like the NNConv calls: the launches
+ * enqueued, >= 0, or -(MP_ERR_* code) with the reason in mp_last_error();
+ * mp_readout_path / mp_readout_chunk: the answer, or -MP_ERR_ARG for C < 1 (or
+ * n_g < 0). */
+int64_t mp_readout_path(int64_t n_g, int32_t C);
+int64_t mp_readout_chunk(int32_t C);
+size_t mp_readout_workspace(int64_t n, int64_t n_graphs, int64_t max_n, int32_t C);
+int64_t mp_attention_readout_f32(const float* x, int64_t ldx, int64_t n, int32_t C, const int64_t* starts,
+                                 int64_t n_graphs, int64_t max_n, const float* q, int64_t ldq, const float* score,
+                                 float* out, int64_t ldo, size_t out_bytes, float* q_out, size_t q_out_bytes,
+                                 float* e, size_t e_bytes, float* stats, size_t stats_bytes, float* alpha,
+                                 size_t alpha_bytes, void* ws, size_t ws_bytes, void* stream);
+int64_t mp_attention_readout_bwd_f32(const float* dr, int64_t lddr, const float* x, int64_t ldx, int64_t n, int32_t C,
+                                     const int64_t* starts, int64_t n_graphs, int64_t max_n, const float* q,
+                                     int64_t ldq, const float* e, const float* stats, const float* r, int64_t ldr,
+                                     float* dx, int64_t lddx, size_t dx_bytes, float* dq, int64_t lddq,
+                                     size_t dq_bytes, float* dscore, size_t dscore_bytes, void* ws, size_t ws_bytes,
+                                     void* stream);
+
 /* ---- TopKPooling: score, per-graph select, gate, filter_adj (csrc/mp_pool.hip)
  * PyG 1.4.3 nn.pool.topk_pool [U] as one deterministic native path: no atomics
  * on values (two integer counters and one integer maximum aside), no dense

@@ -211,6 +211,14 @@ SIGNATURES = {
     "mp_nnconv_aggregate_gather_f32": (i64, [ctypes.POINTER(MpCsr), c_p, i64, i64, i32, c_p, i64, i32, c_p, c_p, c_p,
                                              i64, c_p]),
     "mp_nnconv_edge_grad_f32": (i64, [c_p, c_p, i64, c_p, i64, c_p, i64, i32, i32, c_p, i64, sz, c_p]),
+    # the attention readout (csrc/mp_glob.hip): int64 returns again, the sign tested by ops._count_call
+    "mp_readout_path": (i64, [i64, i32]),          # an answer (0, 1 or 2), or -MP_ERR_ARG
+    "mp_readout_chunk": (i64, [i32]),              # nodes per chunk of a split graph, or -MP_ERR_ARG
+    "mp_readout_workspace": (sz, [i64, i64, i64, i32]),
+    "mp_attention_readout_f32": (i64, [c_p, i64, i64, i32, c_p, i64, i64, c_p, i64, c_p, c_p, i64, sz, c_p, sz, c_p,
+                                       sz, c_p, sz, c_p, sz, c_p, sz, c_p]),
+    "mp_attention_readout_bwd_f32": (i64, [c_p, i64, c_p, i64, i64, i32, c_p, i64, i64, c_p, i64, c_p, c_p, c_p, i64,
+                                           c_p, i64, sz, c_p, i64, sz, c_p, sz, c_p, sz, c_p]),
 }
 
 # Of the symbols declared `int` / `int32_t`, these answer a question (a version,

@@ -2010,6 +2010,23 @@ def cached_batch_layout(batch, n, device=None):
     return _layout_cache.get(batch, ("layout", batch.data_ptr(), int(n)), lambda: batch_layout(batch, n, device))
 
 
+def cached_batch_layout_for(batch, n, n_graphs, device=None):
+    """The cached layout of a sorted batch, with trailing graphs without nodes up
+    to n_graphs (a caller's size= beyond batch.max() + 1): starts padded with n,
+    built once per (batch tensor, n_graphs) and cached like the layout itself.
+    The plain layout when it is unsorted or holds n_graphs graphs or more."""
+    layout = cached_batch_layout(batch, n, device)
+    if layout.unsorted or layout.n_graphs >= n_graphs:
+        return layout
+
+    def extend():
+        starts = torch.cat([layout.starts, layout.starts[-1:].expand(n_graphs - layout.n_graphs)])
+        return BatchLayout(starts, n_graphs, layout.max_n, 0, layout.n)
+    if batch is None:
+        return extend()
+    return _layout_cache.get(batch, ("layout_for", batch.data_ptr(), int(n), int(n_graphs)), extend)
+
+
 _graphs_cache = _Cache()
 
 
@@ -2603,3 +2620,147 @@ def point_edge_features(x_src, pos_src, pos_dst, src, dst):
     check_row_index(src, pos_src.shape[0], "point_edge_features")
     check_row_index(dst, pos_dst.shape[0], "point_edge_features")
     return _PointEdgeFeatures.apply(x_src, pos_src, pos_dst, src, dst)
+
+
+# ---------------------------------------------------------------------------
+# Attention readout (PyG 1.4.3 nn.glob.Set2Set / GlobalAttention [U]; csrc/mp_glob.hip)
+# ---------------------------------------------------------------------------
+
+def readout_path(n_g, C):
+    """0 = one wave, 1 = one workgroup, 2 = split into chunks: how the attention
+    readout reduces a graph of n_g nodes and C channels (mp_readout_path; needs
+    no GPU).  ValueError for C < 1."""
+    p = int(_lib.native().mp_readout_path(int(n_g), int(C)))
+    if p < 0:
+        raise ValueError("readout_path: n_g = %d, C = %d (n_g >= 0 and C >= 1)" % (n_g, C))
+    return p
+
+
+def readout_chunk(C):
+    """Nodes per chunk of a graph on path 2 (mp_readout_chunk; needs no GPU)."""
+    c = int(_lib.native().mp_readout_chunk(int(C)))
+    if c < 0:
+        raise ValueError("readout_chunk: C = %d < 1" % C)
+    return c
+
+
+def _readout_ws(nat, layout, n, C, dev):
+    wsb = nat.mp_readout_workspace(n, layout.n_graphs, layout.max_n, C)
+    return torch.empty(wsb, dtype=torch.uint8, device=dev), wsb
+
+
+class _AttentionReadout(torch.autograd.Function):
+    """r_g = sum_n softmax_g(e)_n x_n with e = x . q[g] (q given) or e = score, in
+    one pass (mp_attention_readout_f32); saves x, q, e, (m, den) and r, and the
+    backward is one pass again (mp_attention_readout_bwd_f32).  Gradients nobody
+    needs are not computed."""
+
+    @staticmethod
+    def forward(ctx, x, q, score, layout, out, col):
+        nat = _lib.native()
+        n, C = x.shape
+        G = layout.n_graphs
+        dev = x.device
+        given = out is not None
+        if not given:
+            out = torch.empty((G, C), dtype=torch.float32, device=dev)
+            col = 0
+        r = out[:, col:col + C]
+        q_out = out[:, :C] if (q is not None and col >= C) else None
+        e = torch.empty(n, dtype=torch.float32, device=dev)
+        stats = torch.empty((G, 2), dtype=torch.float32, device=dev)
+        ws, wsb = _readout_ws(nat, layout, n, C, dev)
+        nz, gz = n > 0, G > 0
+        # the pointers select the mode; a score vector of no nodes has none, and is never read
+        score_ptr = None if score is None else (score.data_ptr() if nz else stats.data_ptr())
+        _count_call(nat, "mp_attention_readout_f32", _lib.ptr(x if nz else None), x.stride(0), n, C,
+                    layout.starts.data_ptr(), G, layout.max_n, _lib.ptr(q), 0 if q is None else q.stride(0),
+                    score_ptr, _lib.ptr(r if gz else None), out.stride(0), _strided_bytes(r),
+                    _lib.ptr(q_out), 0 if q_out is None else _strided_bytes(q_out), _lib.ptr(e if nz else None),
+                    _lib.nbytes(e), _lib.ptr(stats if gz else None), _lib.nbytes(stats), None, 0, ws.data_ptr(), wsb,
+                    _lib.stream_ptr(dev))
+        ctx.layout, ctx.query, ctx.col, ctx.q_copied = layout, q is not None, col, q_out is not None
+        if given:
+            ctx.mark_dirty(out)
+        ctx.save_for_backward(x, q, e, stats, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out):
+        nat = _lib.native()
+        x, q, e, stats, out = ctx.saved_tensors
+        layout, col = ctx.layout, ctx.col
+        n, C = x.shape
+        G = layout.n_graphs
+        dev = x.device
+        r = out[:, col:col + C]
+        dr = g_out[:, col:col + C]
+        if dr.stride(1) != 1 or dr.stride(0) < C:                    # a broadcast gradient (out.sum(0)) has row stride 0
+            dr = dr.contiguous()
+        need_x, need_q, need_s = ctx.needs_input_grad[0], ctx.query and ctx.needs_input_grad[1], \
+            (not ctx.query) and ctx.needs_input_grad[2]
+        dx = torch.empty((n, C), dtype=torch.float32, device=dev) if need_x else None
+        dq = torch.empty((G, C), dtype=torch.float32, device=dev) if need_q else None
+        ds = torch.empty(n, dtype=torch.float32, device=dev) if need_s else None
+        ws, wsb = _readout_ws(nat, layout, n, C, dev)
+        nz, gz = n > 0, G > 0
+        _count_call(nat, "mp_attention_readout_bwd_f32", _lib.ptr(dr if gz else None), dr.stride(0),
+                    _lib.ptr(x if nz else None), x.stride(0), n, C, layout.starts.data_ptr(), G, layout.max_n,
+                    _lib.ptr(q), 0 if q is None else q.stride(0), _lib.ptr(e if nz else None),
+                    _lib.ptr(stats if gz else None), _lib.ptr(r if gz else None), r.stride(0),
+                    _lib.ptr(dx if nz else None), C, _lib.nbytes(dx), _lib.ptr(dq if gz else None), C, _lib.nbytes(dq),
+                    _lib.ptr(ds if nz else None), _lib.nbytes(ds), ws.data_ptr(), wsb, _lib.stream_ptr(dev))
+        if ctx.q_copied and need_q:                                   # columns 0 .. C of out are q itself
+            dq = dq + g_out[:, :C]
+        return dx, dq, ds, None, None, None
+
+
+def _strided_bytes(t):
+    """Extent in bytes of the rows of a 2-D view from its first element on."""
+    return 0 if t.shape[0] == 0 else ((t.shape[0] - 1) * t.stride(0) + t.shape[1]) * t.element_size()
+
+
+def attention_readout(x, layout, q=None, score=None, out=None, col=0):
+    """The softmax-weighted per-graph sum of x's rows (include/mi355_mp.h
+    "Attention readout"): x float32 [n, C]; layout: the BatchLayout of a sorted
+    batch vector (cached_batch_layout); exactly one of q float32 [G, C] (e = x .
+    q[graph]) and score float32 [n] (e = score).  Returns r [G, C], or, with out
+    (float32 [G, W], fresh memory) given, out itself with r written into its
+    columns col .. col + C (out is modified in place); in query mode with col >=
+    C the columns 0 .. C receive q (Set2Set's q_star = [q | r] with col = C, W
+    = 2C).
+    Differentiable in x and q or score.  Tensors must be on the GPU."""
+    _lib.require_device(x, q, score, out, layout.starts)
+    if (q is None) == (score is None):
+        raise ValueError("mi355_mp: attention_readout takes exactly one of q and score")
+    if layout.unsorted:
+        raise ValueError("mi355_mp: batch must be sorted (it descends %d times)" % layout.unsorted)
+    x = _f32_2d(x, "x")
+    n, C = x.shape
+    if C < 1:
+        raise ValueError("mi355_mp: attention_readout needs at least one channel")
+    if x.stride(0) < C:
+        x = x.contiguous()
+    if n != layout.n:
+        raise ValueError("mi355_mp: x has %d rows, the batch layout %d" % (n, layout.n))
+    G = layout.n_graphs
+    if G == 0:
+        return x.new_zeros((0, C if out is None else out.shape[1]))
+    if q is not None:
+        q = _f32_2d(q, "q")
+        if q.shape != (G, C):
+            raise ValueError("mi355_mp: q must be [%d, %d] (got %s)" % (G, C, tuple(q.shape)))
+        if q.stride(0) < C:
+            q = q.contiguous()
+    else:
+        if score.dtype != torch.float32 or score.numel() != n:
+            raise ValueError("mi355_mp: score must be float32 with %d entries (got %s %s)"
+                             % (n, score.dtype, tuple(score.shape)))
+        score = score.reshape(-1).contiguous()
+    if out is not None:
+        if out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] != G or out.stride(1) != 1 \
+                or col < 0 or col + C > out.shape[1] or out.stride(0) < out.shape[1]:
+            raise ValueError("mi355_mp: out must be float32 [%d, >= %d] with unit column stride" % (G, col + C))
+        if out.requires_grad:
+            raise ValueError("mi355_mp: out is overwritten in place and must not require a gradient")
+    return _AttentionReadout.apply(x, q, score, layout, out, int(col))

@@ -1,6 +1,6 @@
 from .conv import MessagePassing, GCNConv, GATConv, SAGEConv, GraphConv, ChebConv, AGNNConv, SGConv, GINConv, SplineConv
 from .conv import PointConv, NNConv
-from .glob import global_add_pool, global_mean_pool, global_max_pool
+from .glob import global_add_pool, global_mean_pool, global_max_pool, Set2Set, GlobalAttention
 from .pool import (TopKPooling, voxel_grid, consecutive_cluster, max_pool, max_pool_x, avg_pool, avg_pool_x, pool_edge,
                    pool_batch, pool_pos, graclus, fps, radius, radius_graph)
 from .data_parallel import DataParallel
@@ -9,4 +9,5 @@ from . import inits  # noqa: F401
 __all__ = ["MessagePassing", "GCNConv", "GATConv", "SAGEConv", "GraphConv", "ChebConv", "AGNNConv", "SGConv",
            "GINConv", "SplineConv", "global_add_pool", "global_mean_pool", "global_max_pool", "TopKPooling",
            "voxel_grid", "consecutive_cluster", "max_pool", "max_pool_x", "avg_pool", "avg_pool_x", "pool_edge",
-           "pool_batch", "pool_pos", "graclus", "fps", "radius", "radius_graph", "PointConv", "NNConv", "DataParallel"]
+           "pool_batch", "pool_pos", "graclus", "fps", "radius", "radius_graph", "PointConv", "NNConv", "Set2Set",
+           "GlobalAttention", "DataParallel"]

@@ -1,5 +1,6 @@
-"""torch_geometric.transforms (PyG 1.4.3): the transform SplineConv's models
-need to turn node positions into pseudo-coordinates."""
+"""torch_geometric.transforms (PyG 1.4.3): the transforms the example models
+need: Cartesian (SplineConv's pseudo-coordinates), Distance (the QM9 NNConv
+example's edge attribute) and Compose."""
 import torch
 
 
@@ -39,4 +40,54 @@ class Cartesian(object):
         return "{}(norm={}, max_value={})".format(self.__class__.__name__, self.norm, self.max)
 
 
-__all__ = ["Cartesian"]
+class Distance(object):
+    r"""Saves the Euclidean distance of linked nodes in its edge attributes:
+    ``||pos[col] - pos[row]||_2`` per edge, as a column.
+
+    Args:
+        norm (bool): divide by the largest distance of the graph, or by
+            ``max_value``. (default: True)
+        max_value (float, optional): the normaliser. (default: None)
+        cat (bool): concatenate to an existing ``edge_attr`` instead of
+            replacing it. (default: True)
+    """
+
+    def __init__(self, norm=True, max_value=None, cat=True):
+        self.norm = norm
+        self.max = max_value
+        self.cat = cat
+
+    def __call__(self, data):
+        (row, col), pos, pseudo = data.edge_index, data.pos, data.edge_attr
+        dist = torch.norm(pos[col] - pos[row], p=2, dim=-1).view(-1, 1)
+        if self.norm and dist.numel() > 0:
+            dist = dist / (dist.max() if self.max is None else self.max)
+        if pseudo is not None and self.cat:
+            pseudo = pseudo.view(-1, 1) if pseudo.dim() == 1 else pseudo
+            data.edge_attr = torch.cat([pseudo, dist.type_as(pseudo)], dim=-1)
+        else:
+            data.edge_attr = dist
+        return data
+
+    def __repr__(self):
+        return "{}(norm={}, max_value={})".format(self.__class__.__name__, self.norm, self.max)
+
+
+class Compose(object):
+    """Composes several transforms: each is applied to the result of the one
+    before it."""
+
+    def __init__(self, transforms):
+        self.transforms = transforms
+
+    def __call__(self, data):
+        for t in self.transforms:
+            data = t(data)
+        return data
+
+    def __repr__(self):
+        args = ["    {},".format(t) for t in self.transforms]
+        return "{}([\n{}\n])".format(self.__class__.__name__, "\n".join(args))
+
+
+__all__ = ["Cartesian", "Distance", "Compose"]
