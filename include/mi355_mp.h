@@ -797,6 +797,82 @@ int64_t mp_attention_readout_bwd_f32(const float* dr, int64_t lddr, const float*
                                      size_t dq_bytes, float* dscore, size_t dscore_bytes, void* ws, size_t ws_bytes,
                                      void* stream);
 
+/* ---- RGCNConv: relational aggregation over a basis decomposition (csrc/mp_rgcn.hip)
+ * PyG 1.4.3's nn.conv.RGCNConv [U] builds W_r = sum_b att[r, b] basis[b], gathers
+ * one [Cin, Cout] matrix per edge and runs E mat-vecs (x = None: an [R*N, Cout]
+ * table every forward).  With edge_type t_e in [0, R), the edge norm n_e, the
+ * per-edge coefficients a_e = n_e att[t_e, :] in R^B and V = basis viewed as
+ * [B*Cin, Cout]:
+ *   sum_{e -> i} n_e x_j W_{t_e} = (sum_{e -> i} a_e (x) x_j) V
+ * one segmented pass and one dense node-level GEMM (the caller's).  a_e is never
+ * stored: the kernels read edge_type (int64) and edge_norm (fp32, or NULL = 1),
+ * both [n_type_edges] in ORIGINAL edge order, through g->eid, and att [R, ld_att
+ * >= B] (att_bytes: its extent, at least ((R - 1) * ld_att + B) floats).
+ * n_type_edges must cover the edge-id space of g (g->n_ids, or g->n_edges when
+ * that is 0).  Types outside [0, R) are the caller's to reject (mi355_mp.ops does,
+ * once per edge_type tensor, with an IndexError); the kernels never read att with
+ * one: such a slot contributes nothing.
+ * Limits (mp_rgcn_ok != 0): 1 <= R <= 65536, B >= 1, Cin >= 1, Cout >= 1 and
+ * B * Cin, B * Cout <= 2^20 floats (one row of Z or Y); the calls apply them to
+ * their own (R, B, C) or (R, B, F).  Accumulators live in registers, tiled over
+ * the grid: neither LDS nor the register file bounds a shape.  att is read
+ * through the cache at every size.
+ * The aggregate calls walk g->rowptr / col / eid only (col and eid required); one
+ * owner per output entry visits its row's slots in slot order and adds left to
+ * right (gather: b = 0..B-1 inside a slot): fp32, deterministic, no atomics.  Rows
+ * of any length are summed serially; hub rows are not split.  Every output entry
+ * of every row is written exactly once (zeros for rows without slots); padding
+ * is left untouched.  One operand of each is addressed by TWO strides:
+ *   mp_rgcn_aggregate_bins_f32 (x [n_cols, ldx >= C]):
+ *     out[r*ld_node + b*ld_block + c] = sum_{slots of r} (n[eid] * att[type[eid], b]) * x[col, c]
+ *     Z [N, B*C]: ld_node = its row stride, ld_block = C.  d basis [B, N, Cout] of
+ *     the featureless backward, in place: ld_node = Cout, ld_block = N*Cout.  The
+ *     entries must not overlap (ld_block >= C and ld_node >= (B-1)*ld_block + C,
+ *     or ld_node >= C and ld_block >= (n_rows-1)*ld_node + C); out_bytes: the
+ *     extent of out, at least ((n_rows-1)*ld_node + (B-1)*ld_block + C) floats.
+ *     Lanes run over the flattened (b, c) for C < 32, over c with 16 values of b
+ *     per lane from C = 32 on.
+ *   mp_rgcn_aggregate_gather_f32:
+ *     out[r, f] = sum_{slots of r} sum_b (n[eid] * att[type[eid], b]) * y[col*ld_node + b*ld_block + f] (+ bias[f])
+ *     Y = x @ L' or dZ, [N, B, F]: ld_node = its row stride, ld_block = F.  basis
+ *     [B, N, Cout] read in place: ld_node = Cout, ld_block = N*Cout.  ld_node,
+ *     ld_block, ldo >= F; y_bytes: the extent of y, at least ((g->n_cols-1)*ld_node
+ *     + (B-1)*ld_block + F) floats.  Lanes run over f.
+ *   mp_rgcn_att_grad_f32 (a relation plan: perm [n_edges] int64, the edge ids
+ *     stably sorted by type, relptr [R + 1] int64, relation r owning the positions
+ *     [relptr[r], relptr[r+1]) of perm; rows / cols [n_edges] int64, each edge's
+ *     node of P and of Q, range-checked by the caller; edge_norm [n_edges] or NULL):
+ *     datt[r, b] = sum_{i in relation r, e = perm[i]} n_e * sum_c P[rows[e]*ldp_node + b*ldp_block + c] * Q[cols[e]*ldq + c]
+ *     Stage 1: one workgroup per chunk of mp_rgcn_att_chunk() positions of one
+ *     relation sums its B partials in a fixed order into the workspace; stage 2:
+ *     one owner per (r, b) adds the relation's chunk partials in chunk order.  A
+ *     relation without edges gets zeros; every datt[r, b] is written (ld_datt >= B,
+ *     datt_bytes at least ((R-1)*ld_datt + B) floats).  relptr is clamped into
+ *     [0, n_edges] and to non-decreasing as it is read and positions of perm
+ *     outside [0, n_edges) are skipped: a bad plan gives wrong sums, not a write
+ *     outside datt or the workspace.  ws: mp_rgcn_att_grad_workspace(n_edges, R, B)
+ *     bytes, required, one layout (csrc/mp_rgcn.hip RgcnAttWs).
+ * Additions to ABI 7 that return int64_t like the NNConv calls: the launches
+ * enqueued, >= 0, or -(MP_ERR_* code) with the reason in mp_last_error() -- for a
+ * bad argument (-MP_ERR_ARG), before any launch.  mp_rgcn_ok and mp_rgcn_att_chunk
+ * answer a question (0 / 1, the chunk size) and need no GPU. */
+int64_t mp_rgcn_ok(int32_t R, int32_t B, int32_t Cin, int32_t Cout);
+int64_t mp_rgcn_att_chunk(void);
+int64_t mp_rgcn_aggregate_bins_f32(const mp_csr* g, const int64_t* edge_type, const float* edge_norm,
+                                   int64_t n_type_edges, const float* att, int64_t ld_att, size_t att_bytes, int32_t R,
+                                   int32_t B, const float* x, int64_t ldx, int32_t C, float* out, int64_t ld_node,
+                                   int64_t ld_block, size_t out_bytes, void* stream);
+int64_t mp_rgcn_aggregate_gather_f32(const mp_csr* g, const int64_t* edge_type, const float* edge_norm,
+                                     int64_t n_type_edges, const float* att, int64_t ld_att, size_t att_bytes,
+                                     int32_t R, int32_t B, const float* y, int64_t ld_node, int64_t ld_block,
+                                     size_t y_bytes, int32_t F, const float* bias, float* out, int64_t ldo,
+                                     void* stream);
+size_t mp_rgcn_att_grad_workspace(int64_t n_edges, int32_t R, int32_t B);
+int64_t mp_rgcn_att_grad_f32(const int64_t* perm, const int64_t* relptr, const int64_t* rows, const int64_t* cols,
+                             int64_t n_edges, const float* edge_norm, const float* P, int64_t ldp_node,
+                             int64_t ldp_block, const float* Q, int64_t ldq, int32_t R, int32_t B, int32_t C,
+                             float* datt, int64_t ld_datt, size_t datt_bytes, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- TopKPooling: score, per-graph select, gate, filter_adj (csrc/mp_pool.hip)
  * PyG 1.4.3 nn.pool.topk_pool [U] as one deterministic native path: no atomics
  * on values (two integer counters and one integer maximum aside), no dense

@@ -219,6 +219,16 @@ SIGNATURES = {
                                        sz, c_p, sz, c_p, sz, c_p, sz, c_p]),
     "mp_attention_readout_bwd_f32": (i64, [c_p, i64, c_p, i64, i64, i32, c_p, i64, i64, c_p, i64, c_p, c_p, c_p, i64,
                                            c_p, i64, sz, c_p, i64, sz, c_p, sz, c_p, sz, c_p]),
+    # RGCNConv (csrc/mp_rgcn.hip): int64 returns again, the sign tested by ops._count_call
+    "mp_rgcn_ok": (i64, [i32, i32, i32, i32]),     # an answer (0 or 1), not a status
+    "mp_rgcn_att_chunk": (i64, []),                # edges per stage-1 workgroup of the att gradient
+    "mp_rgcn_aggregate_bins_f32": (i64, [ctypes.POINTER(MpCsr), c_p, c_p, i64, c_p, i64, sz, i32, i32, c_p, i64, i32,
+                                         c_p, i64, i64, sz, c_p]),
+    "mp_rgcn_aggregate_gather_f32": (i64, [ctypes.POINTER(MpCsr), c_p, c_p, i64, c_p, i64, sz, i32, i32, c_p, i64, i64,
+                                           sz, i32, c_p, c_p, i64, c_p]),
+    "mp_rgcn_att_grad_workspace": (sz, [i64, i32, i32]),
+    "mp_rgcn_att_grad_f32": (i64, [c_p, c_p, c_p, c_p, i64, c_p, c_p, i64, i64, c_p, i64, i32, i32, i32, c_p, i64, sz,
+                                   c_p, sz, c_p]),
 }
 
 # Of the symbols declared `int` / `int32_t`, these answer a question (a version,

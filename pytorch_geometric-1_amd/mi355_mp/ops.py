@@ -1669,6 +1669,291 @@ def nnconv_propagate(graph, x, h, head_weight, head_bias, reduce, form=None, bia
 
 
 # ---------------------------------------------------------------------------
+# RGCNConv: relational aggregation over a basis decomposition (csrc/mp_rgcn.hip)
+# ---------------------------------------------------------------------------
+
+def rgcn_ok(R, B, c_in, c_out):
+    """Whether (R, B, Cin, Cout) lies inside the fused path's limits (mp_rgcn_ok)."""
+    return bool(_lib.native().mp_rgcn_ok(int(R), int(B), int(c_in), int(c_out)))
+
+
+def rgcn_att_chunk():
+    """Edges of one relation per stage-1 workgroup of rgcn_att_grad (mp_rgcn_att_chunk; needs no GPU)."""
+    return int(_lib.native().mp_rgcn_att_chunk())
+
+
+class RelationPlan(object):
+    """The edges grouped by relation: perm (device int64 [E], the edge ids stably
+    sorted by type) and relptr (device int64 [R + 1]; relation r owns positions
+    [relptr[r], relptr[r + 1]) of perm).  Every type lies in [0, R)."""
+    __slots__ = ("perm", "relptr", "n_relations", "n_edges")
+
+    def __init__(self, perm, relptr, n_relations, n_edges):
+        self.perm, self.relptr, self.n_relations, self.n_edges = perm, relptr, n_relations, n_edges
+
+
+_rgcn_plan_cache = _Cache()
+
+
+def rgcn_relation_plan(edge_type, R):
+    """RelationPlan of edge_type (int64 [E] on the device) for R relations: one
+    stable device sort, whose two ends are the range check -- a type outside
+    [0, R) raises IndexError here, before any kernel reads att with it.  Cached
+    on the edge_type tensor (identity + version counter, as the CSR and batch
+    layout caches): one sort and one host read the first time a tensor is seen."""
+    _lib.require_device(edge_type)
+    if edge_type.dtype != torch.int64 or edge_type.dim() != 1:
+        raise TypeError("mi355_mp: edge_type must be int64 [E] (got %s %s)" % (edge_type.dtype, tuple(edge_type.shape)))
+    R = int(R)
+
+    def build():
+        E, dev = edge_type.numel(), edge_type.device
+        if E == 0:
+            return RelationPlan(torch.empty(0, dtype=torch.int64, device=dev),
+                                torch.zeros(R + 1, dtype=torch.int64, device=dev), R, 0)
+        types, perm = torch.sort(edge_type, stable=True)
+        lo, hi = torch.stack([types[0], types[-1]]).tolist()
+        if lo < 0 or hi >= R:
+            raise IndexError("mi355_mp: edge_type holds values in [%d, %d], the layer has relations 0..%d"
+                             % (lo, hi, R - 1))
+        relptr = torch.searchsorted(types, torch.arange(R + 1, dtype=torch.int64, device=dev))
+        return RelationPlan(perm.contiguous(), relptr.contiguous(), R, E)
+
+    return _rgcn_plan_cache.get(edge_type, ("rgcn_plan", edge_type.data_ptr(), R), build)
+
+
+def _extent_bytes(t):
+    """Bytes from a strided tensor's first element to one past its last (its numel
+    times the element size when it is contiguous; 0 for an empty one)."""
+    if t.numel() == 0:
+        return 0
+    return (sum((n - 1) * s for n, s in zip(t.shape, t.stride())) + 1) * t.element_size()
+
+
+def _rgcn_coef(csr, edge_type, edge_norm, att):
+    """The arguments every aggregate call reads a slot's coefficients through."""
+    att = _nnconv_rows(att, "att")
+    edge_type = edge_type.contiguous()
+    if edge_norm is not None:
+        if edge_norm.dtype != torch.float32 or edge_norm.dim() != 1 or edge_norm.numel() != edge_type.numel():
+            raise ValueError("mi355_mp: edge_norm must be float32 [%d] (got %s %s)"
+                             % (edge_type.numel(), edge_norm.dtype, tuple(edge_norm.shape)))
+        edge_norm = edge_norm.detach().contiguous()
+    keep = (att, edge_type, edge_norm)
+    return keep, (csr.struct("other"), edge_type.data_ptr(), _lib.ptr(edge_norm), edge_type.numel(), att.data_ptr(),
+                  att.stride(0), _extent_bytes(att), att.shape[0], att.shape[1])
+
+
+def _rgcn_blocks(t, what):
+    """A [B, n, C] operand addressed in place: (tensor, ld_node, ld_block)."""
+    if t.dtype != torch.float32 or t.dim() != 3:
+        raise TypeError("mi355_mp: %s must be float32 [B, n, C] (got %s %s)" % (what, t.dtype, tuple(t.shape)))
+    if t.stride(2) != 1 or t.stride(1) < t.shape[2] or t.stride(0) < t.shape[1] * t.stride(1):
+        t = t.contiguous()
+    return t, t.stride(1), t.stride(0)
+
+
+def rgcn_bins(csr, edge_type, edge_norm, att, x, out=None):
+    """out[r, b, c] = sum over the slots of r of (norm[eid] * att[type[eid], b]) *
+    x[col[slot], c] (mp_rgcn_aggregate_bins_f32); edge_type int64 [E] and edge_norm
+    (fp32 [E] or None = 1) in edge order, att [R, B], types range-checked by the
+    caller (rgcn_relation_plan).  out: None or a 2-D tensor [n_rows, >= B*C] (Z:
+    entry (b, c) of a row at b*C + c), or a 3-D tensor [B, n_rows, C] written in
+    place through its strides (d basis of the featureless layer).  No autograd."""
+    nat = _lib.native()
+    x = _nnconv_rows(x, "x")
+    keep, coef = _rgcn_coef(csr, edge_type, edge_norm, att)
+    B, C = keep[0].shape[1], x.shape[1]
+    if out is None:
+        out = torch.empty((csr.n_rows, B * C), dtype=torch.float32, device=x.device)
+    if out.dim() == 3:
+        if tuple(out.shape) != (B, csr.n_rows, C) or out.stride(2) != 1:
+            raise ValueError("mi355_mp: a 3-D out must be [%d, %d, %d] with unit stride in c" % (B, csr.n_rows, C))
+        ld_node, ld_block = out.stride(1), out.stride(0)
+    else:
+        ld_node, ld_block = out.stride(0), C
+    if csr.n_rows:
+        _count_call(nat, "mp_rgcn_aggregate_bins_f32", *coef, x.data_ptr(), x.stride(0), C, out.data_ptr(), ld_node,
+                    ld_block, _extent_bytes(out), _lib.stream_ptr(x.device))
+    return out
+
+
+def rgcn_gather(csr, edge_type, edge_norm, att, y, F=None, bias=None, out=None):
+    """out[r, f] = sum over the slots of r and b < B of (norm[eid] * att[type[eid], b])
+    * y[col[slot], b, f] (+ bias) (mp_rgcn_aggregate_gather_f32).  y: a 2-D tensor
+    [n_cols, >= B*F] (entry (b, f) of a row at b*F + f; F required), or a 3-D
+    tensor [B, n_cols, F] read in place through its strides (basis itself, for
+    the featureless layer).  No autograd."""
+    nat = _lib.native()
+    keep, coef = _rgcn_coef(csr, edge_type, edge_norm, att)
+    if y.dim() == 3:
+        y, ld_node, ld_block = _rgcn_blocks(y, "y")
+        F = y.shape[2]
+    else:
+        y, F = _nnconv_rows(y, "y"), int(F)
+        ld_node, ld_block = y.stride(0), F
+    if out is None:
+        out = torch.empty((csr.n_rows, F), dtype=torch.float32, device=y.device)
+    if csr.n_rows:
+        _count_call(nat, "mp_rgcn_aggregate_gather_f32", *coef, y.data_ptr(), ld_node, ld_block, _extent_bytes(y), F,
+                    _lib.ptr(bias), out.data_ptr(), out.stride(0), _lib.stream_ptr(y.device))
+    return out
+
+
+def rgcn_att_grad(plan, rows, cols, edge_norm, P, Q, B):
+    """datt[r, b] = sum over the edges e of relation r of norm[e] * sum_c P[rows[e], b,
+    c] * Q[cols[e], c] (mp_rgcn_att_grad_f32): chunk partials in a fixed order,
+    then the relation's chunks in chunk order; zeros for a relation without
+    edges.  P: a 2-D tensor [n, >= B*C] or a 3-D one [B, n, C] read in place; Q
+    [m, C]; rows / cols int64 [E], range-checked by the caller (a CSR built from
+    them has done it).  No autograd."""
+    nat = _lib.native()
+    Q = _nnconv_rows(Q, "Q")
+    C, B = Q.shape[1], int(B)
+    if P.dim() == 3:
+        P, ldp_node, ldp_block = _rgcn_blocks(P, "P")
+    else:
+        P = _nnconv_rows(P, "P")
+        ldp_node, ldp_block = P.stride(0), C
+    rows, cols = rows.contiguous(), cols.contiguous()
+    R, E = plan.n_relations, plan.n_edges
+    if rows.numel() != E or cols.numel() != E:
+        raise ValueError("mi355_mp: the relation plan holds %d edges, rows / cols %d / %d" % (E, rows.numel(), cols.numel()))
+    if edge_norm is not None:
+        if edge_norm.dtype != torch.float32 or edge_norm.numel() != E:
+            raise ValueError("mi355_mp: edge_norm must be float32 [%d] (got %s %s)"
+                             % (E, edge_norm.dtype, tuple(edge_norm.shape)))
+        edge_norm = edge_norm.detach().contiguous()
+    datt = torch.empty((R, B), dtype=torch.float32, device=Q.device)
+    ws_bytes = nat.mp_rgcn_att_grad_workspace(E, R, B)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=Q.device)
+    _count_call(nat, "mp_rgcn_att_grad_f32", plan.perm.data_ptr(), plan.relptr.data_ptr(), rows.data_ptr(),
+                cols.data_ptr(), E, _lib.ptr(edge_norm), P.data_ptr(), ldp_node, ldp_block, Q.data_ptr(), Q.stride(0),
+                R, B, C, datt.data_ptr(), datt.stride(0), _lib.nbytes(datt), ws.data_ptr(), ws_bytes,
+                _lib.stream_ptr(Q.device))
+    return datt
+
+
+def rgcn_form(B, c_in, c_out, E, N):
+    """The featured forward's form, by the floats each form moves (a pure
+    function of the shape; measured in tools/bench_rgcn.py):
+      bins    reads B + Cin floats per edge, writes Z [N, B Cin] and reads it
+              back in the GEMM:            E (B + Cin)          + 2 N B Cin
+      gather  writes Y [N, B Cout] in the GEMM and gathers B + B Cout floats
+              per edge:                    E (B + B Cout)       +   N B Cout
+    The lower count wins, ties to bins (it keeps Z for d basis, the gather form
+    recomputes it in the backward).  The featureless layer has one form."""
+    bins = E * (B + c_in) + 2 * N * B * c_in
+    gather = E * (B + B * c_out) + N * B * c_out
+    return "bins" if bins <= gather else "gather"
+
+
+class _RGCNPropagate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, basis, att, bias, graph, edge_type, edge_norm, plan, form):
+        B, c_in, c_out = basis.shape
+        csr = graph.dst
+        Z = None
+        if x is None:                                    # x = identity: row j of every basis[b], in place
+            out = rgcn_gather(csr, edge_type, edge_norm, att, basis, bias=bias)
+        elif form == "bins":
+            Z = rgcn_bins(csr, edge_type, edge_norm, att, x)
+            V = basis.view(B * c_in, c_out)
+            out = torch.mm(Z, V) if bias is None else torch.addmm(bias, Z, V)
+        else:
+            Y = torch.mm(x, basis.permute(1, 0, 2).reshape(c_in, B * c_out))
+            out = rgcn_gather(csr, edge_type, edge_norm, att, Y, c_out, bias=bias)
+        ctx.graph, ctx.plan, ctx.has_bias, ctx.featureless = graph, plan, bias is not None, x is None
+        # the cached Graph holds its edge_index weakly and builds the transposed CSR
+        # on first use, in backward: keep the tensor alive until then
+        ctx.save_for_backward(x, basis, att, edge_type, edge_norm, Z if ctx.needs_input_grad[1] else None,
+                              graph._edge_index())
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, basis, att, edge_type, edge_norm, Z, edge_index = ctx.saved_tensors
+        graph, plan = ctx.graph, ctx.plan
+        B, c_in, c_out = basis.shape
+        g = g.contiguous()
+        gx = gbasis = gatt = gb = None
+        if ctx.has_bias and ctx.needs_input_grad[3]:
+            gb = col_sums(g)
+        want_x, want_basis, want_att = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        dst, src = edge_index[graph.i], edge_index[graph.j]
+        if ctx.featureless:
+            if want_basis:
+                # the transposed pass: rows = source nodes j, gathers destination rows of g, written into
+                # d basis [B, N, Cout] through the block stride
+                gbasis = torch.empty_like(basis, memory_format=torch.contiguous_format)
+                rgcn_bins(graph.src, edge_type, edge_norm, att, g, out=gbasis)
+            if want_att:
+                gatt = rgcn_att_grad(plan, src, dst, edge_norm, basis, g, B)
+            return None, gbasis, gatt, gb, None, None, None, None, None
+        if want_basis:
+            if Z is None:                                # the gather form never built it
+                Z = rgcn_bins(graph.dst, edge_type, edge_norm, att, x)
+            gbasis = torch.mm(Z.t(), g).view(B, c_in, c_out)
+        if want_x or want_att:
+            dZ = torch.mm(g, basis.view(B * c_in, c_out).t())
+            if want_x:
+                gx = rgcn_gather(graph.src, edge_type, edge_norm, att, dZ, c_in)
+            if want_att:
+                gatt = rgcn_att_grad(plan, dst, src, edge_norm, dZ, x, B)
+        return gx, gbasis, gatt, gb, None, None, None, None, None
+
+
+def rgcn_propagate(graph, x, edge_type, edge_norm, att, basis, root=None, bias=None, form=None):
+    """out[i] = sum_{e = (j -> i)} edge_norm[e] * x[j] @ (sum_b att[edge_type[e], b] basis[b]) (+ x[i] @ root) (+ bias)
+
+    RGCNConv's propagate with no per-edge weight matrix: one segmented pass and
+    one node-level GEMM.  basis [B, Cin, Cout], att [R, B], edge_type int64 [E]
+    (range-checked once per tensor: IndexError), edge_norm fp32 [E] without a
+    gradient, or None.  x [N, Cin], or None for the featureless layer (x = the
+    identity, N = Cin): then basis is gathered in place, no [R*N, Cout] table is
+    built, and root [N, Cout] is added as it is.  form None picks by rgcn_form,
+    'bins' / 'gather' force one (featured only).  Deterministic, native forward
+    and backward: d x by the gather kernel over the transposed CSR, d basis = Z^T g
+    (Z saved by the bins form, recomputed after the gather form; featureless: the
+    bins kernel over the transposed CSR, in place), d att by rgcn_att_grad; a
+    launch is skipped when nothing needs its gradient."""
+    if form not in (None, "bins", "gather"):
+        raise ValueError("unknown form %r" % (form,))
+    _lib.require_device(x, edge_type, edge_norm, att, basis, root, bias)
+    if basis.dtype != torch.float32 or basis.dim() != 3:
+        raise ValueError("mi355_mp: basis must be float32 [B, Cin, Cout] (got %s %s)" % (basis.dtype, tuple(basis.shape)))
+    B, c_in, c_out = basis.shape
+    if att.dtype != torch.float32 or att.dim() != 2 or att.shape[1] != B:
+        raise ValueError("mi355_mp: att must be float32 [R, %d] (got %s %s)" % (B, att.dtype, tuple(att.shape)))
+    R = att.shape[0]
+    if edge_norm is not None and edge_norm.requires_grad:
+        raise NotImplementedError("mi355_mp: rgcn_propagate has no gradient with respect to edge_norm")
+    if x is not None:
+        x = _nnconv_rows(x, "x")
+        if x.shape[1] != c_in:
+            raise ValueError("mi355_mp: x has %d columns, basis %d input channels" % (x.shape[1], c_in))
+    elif form is not None:
+        raise ValueError("mi355_mp: the featureless layer (x = None) has one form (got form=%r)" % (form,))
+    n = c_in if x is None else x.shape[0]
+    # the featureless kernels see rows of B * Cout floats only: Cin = N is a node count there
+    if not rgcn_ok(R, B, c_out if x is None else c_in, c_out):
+        raise NotImplementedError("mi355_mp: outside the fused RGCN path's limits: "
+                                  + _lib.native().mp_last_error().decode(errors="replace"))
+    if edge_type.numel() != graph.dst.n_edges:
+        raise ValueError("mi355_mp: edge_type has %d entries, the graph %d edges" % (edge_type.numel(), graph.dst.n_edges))
+    if n != graph.n_src or n != graph.n_dst:
+        raise ValueError("mi355_mp: %d nodes, the graph %d sources and %d destinations" % (n, graph.n_src, graph.n_dst))
+    plan = rgcn_relation_plan(edge_type, R)
+    if form is None and x is not None:
+        form = rgcn_form(B, c_in, c_out, edge_type.numel(), n)
+    basis = basis if basis.is_contiguous() else basis.contiguous()
+    out = _RGCNPropagate.apply(x, basis, att, bias, graph, edge_type, edge_norm, plan, form)
+    if root is not None:
+        out = out + root if x is None else torch.addmm(out, x, root)
+    return out
+
+
+# ---------------------------------------------------------------------------
 # TopKPooling (PyG 1.4.3 nn.pool.topk_pool [U]; csrc/mp_pool.hip)
 # ---------------------------------------------------------------------------
 

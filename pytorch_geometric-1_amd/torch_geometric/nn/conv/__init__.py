@@ -10,6 +10,7 @@ from .gin_conv import GINConv
 from .spline_conv import SplineConv
 from .point_conv import PointConv
 from .nn_conv import NNConv
+from .rgcn_conv import RGCNConv
 
 __all__ = ["MessagePassing", "GCNConv", "GATConv", "SAGEConv", "GraphConv", "ChebConv", "AGNNConv", "SGConv", "GINConv",
-           "SplineConv", "PointConv", "NNConv"]
+           "SplineConv", "PointConv", "NNConv", "RGCNConv"]
