@@ -711,8 +711,14 @@ int mp_spline_aggregate_gather_f32(const mp_csr* g, const float* pseudo, int64_t
  * Like the graclus and point-set entry points these are additions to ABI 7 that
  * return int64_t, not a status: the launches enqueued, >= 0, or -(MP_ERR_* code)
  * with the reason in mp_last_error() when the call is refused -- for a bad
- * argument (-MP_ERR_ARG), before any launch.  The caller tests the sign. */
+ * argument (-MP_ERR_ARG), before any launch.  The caller tests the sign.
+ * mp_nnconv_edge_grad_width(H, Cin): which kernel mp_nnconv_edge_grad_f32 takes
+ * for a shape -- 0 = a lane group per (e, h) pair (Cin <= 32), else the lanes W =
+ * 32 or 64 per (edge, W values of h), the width that wastes the fewest lanes
+ * and values of h (ties to 64) -- or -MP_ERR_ARG for a shape outside the limits.
+ * The call dispatches on this function; it needs no GPU. */
 int64_t mp_nnconv_ok(int32_t H, int32_t Cin, int32_t Cout);
+int64_t mp_nnconv_edge_grad_width(int32_t H, int32_t Cin);
 int64_t mp_nnconv_aggregate_bins_f32(const mp_csr* g, const float* h, int64_t n_h_edges, int64_t ldh, int32_t H,
                                      const float* x, int64_t ldx, int32_t Cin, const float* row_scale, float* out,
                                      int64_t ldo, void* stream);

@@ -269,6 +269,15 @@ __global__ __launch_bounds__(256) void k_nnconv_edge_grad_wave(const int64_t* __
 // host side
 // ---------------------------------------------------------------------------
 
+// The edge gradient's kernel by shape: 0 = a lane group per (e, h) pair (Cin <=
+// kNNConvEdgeGroupMaxCin), else the lanes W = 32 or 64 per (edge, W values of h):
+// the width that wastes the fewest lanes and values of h; ties to 64
+static int nn_edge_grad_width(int32_t H, int32_t Cin) {
+  if (Cin <= kNNConvEdgeGroupMaxCin) return 0;
+  auto used = [&](int64_t W) { return (double)Cin / (ceil_div(Cin, W) * W) * H / (ceil_div(H, W) * W); };
+  return used(32) > used(64) ? 32 : 64;
+}
+
 // One (H, C) pair of the fused path: a row of (H+1) * C floats.
 static int nn_shape(const char* fn, int32_t H, int32_t C, const char* cname) {
   MP_CHECK_ARG(H >= 1, "%s: H = %d < 1", fn, H);
@@ -300,6 +309,11 @@ using namespace mp;
 extern "C" int64_t mp_nnconv_ok(int32_t H, int32_t Cin, int32_t Cout) {
   const char* fn = "mp_nnconv_ok";
   return nn_shape(fn, H, Cin, "Cin") == MP_OK && nn_shape(fn, H, Cout, "Cout") == MP_OK ? 1 : 0;
+}
+
+extern "C" int64_t mp_nnconv_edge_grad_width(int32_t H, int32_t Cin) {
+  if (nn_shape("mp_nnconv_edge_grad_width", H, Cin, "Cin") != MP_OK) return -(int64_t)MP_ERR_ARG;
+  return nn_edge_grad_width(H, Cin);
 }
 
 static int nnconv_bins(const mp_csr* g, const float* h, int64_t n_h_edges, int64_t ldh, int32_t H, const float* x,
@@ -379,7 +393,7 @@ static int nnconv_edge_grad(const int64_t* rows, const int64_t* cols, int64_t n_
   MP_CHECK_ARG(dz != nullptr, "%s: dz is NULL", fn);
   MP_CHECK_ARG(x != nullptr, "%s: x is NULL", fn);
   MP_CHECK_ARG(dh != nullptr, "%s: dh is NULL", fn);
-  if (Cin <= kNNConvEdgeGroupMaxCin) {
+  if (nn_edge_grad_width(H, Cin) == 0) {
     const int glog = nn_group_log2(Cin);
     const int64_t n_pairs = n_edges * H;
     const int64_t blocks = ceil_div(n_pairs << glog, 256);
@@ -389,9 +403,7 @@ static int nnconv_edge_grad(const int64_t* rows, const int64_t* cols, int64_t n_
     hipLaunchKernelGGL(k_nnconv_edge_grad, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), rows, cols,
                        n_pairs, dz, lddz, x, ldx, H, Cin, glog, dh, lddh);
   } else {
-    // the group width that wastes the fewest lanes and values of h; ties to 64
-    auto used = [&](int64_t W) { return (double)Cin / (ceil_div(Cin, W) * W) * H / (ceil_div(H, W) * W); };
-    const int W = used(32) > used(64) ? 32 : 64;
+    const int W = nn_edge_grad_width(H, Cin);
     const int64_t bx = ceil_div(n_edges, 4 * (64 / W));
     const int64_t by = ceil_div(H, W);
     MP_CHECK_ARG(bx <= 0x7fffffff && by <= 65535, "%s: grid too large (n_edges %lld, H %d)", fn, (long long)n_edges,

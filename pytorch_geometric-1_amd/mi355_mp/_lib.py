@@ -206,6 +206,7 @@ SIGNATURES = {
                                                   i64, sz, c_p]),
     # NNConv (csrc/mp_nnconv.hip): int64 returns like the two groups above, the sign tested by ops._count_call
     "mp_nnconv_ok": (i64, [i32, i32, i32]),        # an answer (0 or 1), not a status
+    "mp_nnconv_edge_grad_width": (i64, [i32, i32]),  # an answer (0, 32 or 64), or -MP_ERR_ARG
     "mp_nnconv_aggregate_bins_f32": (i64, [ctypes.POINTER(MpCsr), c_p, i64, i64, i32, c_p, i64, i32, c_p, c_p, i64,
                                            c_p]),
     "mp_nnconv_aggregate_gather_f32": (i64, [ctypes.POINTER(MpCsr), c_p, i64, i64, i32, c_p, i64, i32, c_p, c_p, c_p,

@@ -1476,6 +1476,16 @@ def nnconv_ok(H, c_in, c_out):
     return bool(_lib.native().mp_nnconv_ok(int(H), int(c_in), int(c_out)))
 
 
+def nnconv_edge_grad_width(H, c_in):
+    """The kernel nnconv_edge_grad takes for a shape: 0 = a lane group per (e, h)
+    pair (Cin <= 32), else its 32 or 64 lanes per (edge, 32 or 64 values of h)
+    (mp_nnconv_edge_grad_width; needs no GPU)."""
+    w = int(_lib.native().mp_nnconv_edge_grad_width(int(H), int(c_in)))
+    if w < 0:
+        raise ValueError("mi355_mp: " + _lib.native().mp_last_error().decode(errors="replace"))
+    return w
+
+
 def _nnconv_rows(t, what):
     t = _f32_2d(t, what)
     return t if t.stride(0) >= max(t.shape[1], 1) else t.contiguous()
@@ -1513,15 +1523,18 @@ def nnconv_gather(csr, h, y, F, row_scale=None, bias=None, out=None):
     return out
 
 
-def nnconv_edge_grad(rows, cols, dz, x, H):
+def nnconv_edge_grad(rows, cols, dz, x, H, out=None):
     """dh[e, k] = sum_c dz[rows[e], k*Cin + c] * x[cols[e], c] for k < H
     (mp_nnconv_edge_grad_f32); rows / cols int64 [E], range-checked by the
-    caller (a CSR built from them has done it).  No autograd."""
+    caller (a CSR built from them has done it).  out: a contiguous float32 [E, H]
+    tensor to write into.  No autograd."""
     nat = _lib.native()
     dz, x = _nnconv_rows(dz, "dz"), _nnconv_rows(x, "x")
     rows, cols = rows.contiguous(), cols.contiguous()
     E, H = rows.numel(), int(H)
-    dh = torch.empty((E, H), dtype=torch.float32, device=x.device)
+    if out is not None and not (out.dtype == torch.float32 and tuple(out.shape) == (E, H) and out.is_contiguous()):
+        raise ValueError("mi355_mp: out must be a contiguous float32 [%d, %d] tensor" % (E, H))
+    dh = torch.empty((E, H), dtype=torch.float32, device=x.device) if out is None else out
     if E:
         _count_call(nat, "mp_nnconv_edge_grad_f32", rows.data_ptr(), cols.data_ptr(), E, dz.data_ptr(), dz.stride(0),
                     x.data_ptr(), x.stride(0), H, x.shape[1], dh.data_ptr(), dh.stride(0), _lib.nbytes(dh),
@@ -1646,7 +1659,8 @@ def nnconv_propagate(graph, x, h, head_weight, head_bias, reduce, form=None, bia
     if form not in (None, "bins", "gather"):
         raise ValueError("unknown form %r" % (form,))
     _lib.require_device(x, h, head_weight, head_bias, bias)
-    x, h = _nnconv_rows(x, "x"), _nnconv_rows(h, "h")
+    # x also feeds a GEMM (x L' of the gather form), whose rounding follows the operand layout: one layout
+    x, h = _f32_2d(x, "x").contiguous(), _nnconv_rows(h, "h")
     H, c_in = h.shape[1], x.shape[1]
     if head_weight.dtype != torch.float32 or head_weight.dim() != 2 or head_weight.shape[1] != H \
             or c_in == 0 or head_weight.shape[0] % max(c_in, 1):
@@ -1800,13 +1814,14 @@ def rgcn_gather(csr, edge_type, edge_norm, att, y, F=None, bias=None, out=None):
     return out
 
 
-def rgcn_att_grad(plan, rows, cols, edge_norm, P, Q, B):
+def rgcn_att_grad(plan, rows, cols, edge_norm, P, Q, B, out=None):
     """datt[r, b] = sum over the edges e of relation r of norm[e] * sum_c P[rows[e], b,
     c] * Q[cols[e], c] (mp_rgcn_att_grad_f32): chunk partials in a fixed order,
     then the relation's chunks in chunk order; zeros for a relation without
     edges.  P: a 2-D tensor [n, >= B*C] or a 3-D one [B, n, C] read in place; Q
     [m, C]; rows / cols int64 [E], range-checked by the caller (a CSR built from
-    them has done it).  No autograd."""
+    them has done it).  out: a contiguous float32 [R, B] tensor to write into.
+    No autograd."""
     nat = _lib.native()
     Q = _nnconv_rows(Q, "Q")
     C, B = Q.shape[1], int(B)
@@ -1824,7 +1839,9 @@ def rgcn_att_grad(plan, rows, cols, edge_norm, P, Q, B):
             raise ValueError("mi355_mp: edge_norm must be float32 [%d] (got %s %s)"
                              % (E, edge_norm.dtype, tuple(edge_norm.shape)))
         edge_norm = edge_norm.detach().contiguous()
-    datt = torch.empty((R, B), dtype=torch.float32, device=Q.device)
+    if out is not None and not (out.dtype == torch.float32 and tuple(out.shape) == (R, B) and out.is_contiguous()):
+        raise ValueError("mi355_mp: out must be a contiguous float32 [%d, %d] tensor" % (R, B))
+    datt = torch.empty((R, B), dtype=torch.float32, device=Q.device) if out is None else out
     ws_bytes = nat.mp_rgcn_att_grad_workspace(E, R, B)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=Q.device)
     _count_call(nat, "mp_rgcn_att_grad_f32", plan.perm.data_ptr(), plan.relptr.data_ptr(), rows.data_ptr(),
@@ -1929,7 +1946,9 @@ def rgcn_propagate(graph, x, edge_type, edge_norm, att, basis, root=None, bias=N
     if edge_norm is not None and edge_norm.requires_grad:
         raise NotImplementedError("mi355_mp: rgcn_propagate has no gradient with respect to edge_norm")
     if x is not None:
-        x = _nnconv_rows(x, "x")
+        # one layout for the kernels and the GEMMs (x root, x L'): the GEMM library picks its kernel by the
+        # operand layout, so a strided or transposed view of x would round differently from its contiguous copy
+        x = _f32_2d(x, "x").contiguous()
         if x.shape[1] != c_in:
             raise ValueError("mi355_mp: x has %d columns, basis %d input channels" % (x.shape[1], c_in))
     elif form is not None:

@@ -115,6 +115,9 @@ class NNConv(MessagePassing):
                 raise ValueError("NNConv: form=%r needs the fused path (see NNConv.fused_head)" % (form,))
             return self.propagate(edge_index, x=x, pseudo=pseudo)
         trunk, head = fused
+        # one layout for the kernels and the GEMMs (x root, x L'): the GEMM library picks its kernel by the
+        # operand layout, so a strided or transposed view of x would round differently from its contiguous copy
+        x = x.contiguous()
         h = pseudo
         for module in trunk or ():
             h = module(h)

@@ -51,7 +51,7 @@ def bins(edge_dst, edge_src, n_rows, h, x, row_scale=None):
     ht, x = _ht(h), _cols(x).double()
     terms = ht[:, :, None] * x[edge_src][:, None, :]                   # [E, H+1, Cin]
     Z = torch.zeros(n_rows, terms.shape[1] * terms.shape[2], dtype=torch.float64)
-    Z = Z.index_add(0, edge_dst, terms.reshape(terms.shape[0], -1))
+    Z = Z.index_add(0, edge_dst, terms.reshape(terms.shape[0], Z.shape[1]))
     return Z if row_scale is None else Z * row_scale.double().view(-1, 1)
 
 
@@ -142,10 +142,11 @@ def nn_conv_loop(x, edge_index, h, head_w, head_b, c_in, c_out, root=None, bias=
 
 def assert_bound(got, ref, scale, what):
     """|got - ref| <= 1e-5 * scale elementwise (scale = sum |terms|); prints the largest ratio."""
+    assert tuple(got.shape) == tuple(ref.shape) == tuple(scale.shape), "%s: shapes %s / %s / %s" % (
+        what, tuple(got.shape), tuple(ref.shape), tuple(scale.shape))
     err = (got.detach().cpu().double() - ref.detach()).abs()
     if not err.numel():
         return
-    assert err.shape == scale.shape, "%s: shapes %s / %s" % (what, tuple(err.shape), tuple(scale.shape))
     lim = BOUND * scale.detach()
     worst = float((err - lim).max())
     ratio = float((err / scale.detach().clamp(min=1e-300)).max())

@@ -101,10 +101,11 @@ def rgcn_conv_loop(x, edge_index, edge_type, edge_norm, basis, att, root=None, b
 
 def assert_bound(got, ref, scale, what):
     """|got - ref| <= 1e-5 * scale elementwise (scale = sum |terms|); prints the largest ratio."""
+    assert tuple(got.shape) == tuple(ref.shape) == tuple(scale.shape), "%s: shapes %s / %s / %s" % (
+        what, tuple(got.shape), tuple(ref.shape), tuple(scale.shape))
     err = (got.detach().cpu().double() - ref.detach()).abs()
     if not err.numel():
         return
-    assert err.shape == scale.shape, "%s: shapes %s / %s" % (what, tuple(err.shape), tuple(scale.shape))
     lim = BOUND * scale.detach()
     worst = float((err - lim).max())
     ratio = float((err / scale.detach().clamp(min=1e-300)).max())

@@ -203,3 +203,182 @@ def test_spline_restatement_at_the_edges(N, deg, loops, root, bias):
         want = msg.mean(0, keepdim=True) + (x.double() @ r.double() if root else 0) + (b.double() if bias else 0)
         got = S.spline_conv(x, ei, u, w, r, b, ks, op, M, "mean")
         assert float((got - want).abs().max()) <= 1e-12
+
+
+# ---- NNConv / RGCNConv: the generators, and the restatements on the pinned examples ------------
+
+from tests import _nnconv_ref as NR, _rgcn_ref as RR  # noqa: E402
+
+F64_BOUND = 1e-12          # float64 restatements against each other: 1e-12 * sum |terms|
+
+
+def _close64(a, b, scale, what):
+    assert tuple(a.shape) == tuple(b.shape) == tuple(scale.shape), what
+    if a.numel():
+        excess = float(((a - b).abs() - F64_BOUND * scale).max())
+        assert excess <= 0.0, "%s: exceeds 1e-12 * sum|terms| by %.3g" % (what, excess)
+
+
+@pytest.mark.parametrize("kind", Z.RELATION_KINDS)
+def test_relation_kinds(kind):
+    for E, n_rel in ((0, 1), (0, 7), (1, 1), (5, 2), (300, 1), (300, 2), (300, 3), (300, 7), (640, 30)):
+        for seed in SEEDS:
+            et = Z.relations(kind, E, n_rel, seed)
+            assert et.dtype == torch.int64 and tuple(et.shape) == (E,)
+            assert torch.equal(et, Z.relations(kind, E, n_rel, seed))              # a seed replays
+            if not E:
+                continue
+            assert 0 <= int(et.min()) and int(et.max()) < n_rel
+            count = torch.bincount(et, minlength=n_rel)
+            if kind == "one":
+                assert int(count.max()) == E and (n_rel == 1 or int(count[0]) == 0)
+            if kind == "skewed" and n_rel > 2:
+                assert int(count[1]) == 0                                           # an empty relation
+                if E >= 300:
+                    assert int(count[0]) == int(count.max()) and int((count > 0).sum()) >= min(n_rel - 1, 5)
+            if kind == "uniform" and E >= 300 and n_rel <= 7:
+                assert int(count.min()) > 0
+    assert len({int(Z.relations("one", 4, 7, seed)[0]) for seed in range(12)}) == 6   # every relation but 0
+
+
+def test_edge_norm_and_edge_attr_kinds():
+    assert Z.NORM_KINDS == (None, "rand", "signed") and Z.edge_norm(None, 9, 1) is None
+    for E in (0, 1, 2, 50):
+        for seed in SEEDS:
+            r, s = Z.edge_norm("rand", E, seed), Z.edge_norm("signed", E, seed)
+            assert r.dtype == s.dtype == torch.float32 and tuple(r.shape) == tuple(s.shape) == (E,)
+            assert torch.equal(r, Z.edge_norm("rand", E, seed)) and torch.equal(s, Z.edge_norm("signed", E, seed))
+            if E:
+                assert 0.5 <= float(r.min()) and float(r.max()) < 1.5 and float(s[0]) == 0.0
+            if E == 50:
+                assert int((s == 0).sum()) >= 17 and int((s == 1).sum()) >= 17 and int((s < 0).sum()) >= 8
+                assert int(((s > 0) & (s < 1)).sum()) > 0
+            for D in (1, 3):
+                u = Z.edge_attr(E, D, seed)
+                assert u.dtype == torch.float32 and tuple(u.shape) == (E, D) and torch.equal(u, Z.edge_attr(E, D, seed))
+                if E:
+                    assert 0.0 <= float(u.min()) and float(u.max()) <= 1.0 and float(u[0].abs().max()) == 0.0
+                if E == 50:
+                    assert bool((u == 1).all(1).any()) and bool((u == 0).all(1).any())
+
+
+def test_pinned_conv_examples_are_what_their_comments_say():
+    from tests import _conv_lane_cases as K
+    nn = [(p, Z.nnconv_inputs(p)) for p in Z.NNCONV_PINNED]
+    rg = [(p, Z.rgcn_inputs(p)) for p in Z.RGCN_PINNED]
+    for p, (ei, x, ea) in nn:
+        E = ei.shape[1]
+        assert tuple(x.shape) == (p["N"], p["c_in"]) and ea.shape[0] == E == int(p["N"] * p["deg"])
+        assert ea.shape[1] == (p["H"] if p["nn"] == "linear" else p["D"])
+        if p["loops"] == 1.0:
+            assert bool((ei[0] == ei[1]).all())
+    for p, (ei, x, et, en) in rg:
+        assert et.shape[0] == ei.shape[1] and (x is None) == (p["mode"] == "featureless")
+        assert (en is None) == (p["nkind"] is None)
+        if p["loops"] == 1.0:
+            assert bool((ei[0] == ei[1]).all())
+    shapes = lambda rows: [(p["N"], i[0].shape[1]) for p, i in rows]                 # noqa: E731
+    for rows in (nn, rg):
+        assert (1, 0) in shapes(rows) and (5, 0) in shapes(rows)
+        assert any(p["loops"] == 1.0 and i[0].shape[1] > 10 for p, i in rows)      # every edge a loop
+    assert any(p["N"] == 1 and i[0].shape[1] > 0 for p, i in nn)                     # N = 1, self loops only
+    assert any(p["aggr"] == "mean" and int((torch.bincount(i[0][0], minlength=p["N"])
+                                            + torch.bincount(i[0][1], minlength=p["N"]) == 0).sum()) > 5
+               for p, i in nn)                                                       # mean with isolated nodes
+    assert any(p["form"] == "gather" and not p["head_bias"] for p, _ in nn)
+    linear = {(p["c_in"], p["H"]) for p, _ in nn if p["nn"] == "linear" and p["N"] > 5}
+    assert linear == {(33, 40), (70, 40), (32, 25)}
+    modes = {(p["N"], p["mode"] == "featureless") for p, i in rg if i[0].shape[1] == 0}
+    assert modes >= {(1, False), (1, True), (5, False)}
+    assert any(p["R"] == 1 for p, _ in rg) and any(p["B"] == 65 and p["c_in"] == 3 for p, _ in rg)
+    assert any(p["nkind"] == "signed" for p, _ in rg)
+    assert any(p["rkind"] == "one" and (p["N"], p["deg"]) == (80, 8.0) and int(torch.bincount(i[2]).max()) == 640
+               for p, i in rg)
+    assert K.N_EDGES == 203                                                          # (the sweep's graph, for scale)
+
+
+@pytest.mark.parametrize("k", range(len(Z.NNCONV_PINNED)))
+def test_nnconv_restatements_agree_on_the_pinned_examples(k):
+    """nn_conv against its literal loop, and bins(h, x) @ L against gather(h, x @
+    L'): the identity the two kernel forms rest on (E = 0 and N = 1 included)."""
+    p = Z.NNCONV_PINNED[k]
+    ei, x, ea = Z.nnconv_inputs(p)
+    N, c_in, c_out, H = p["N"], p["c_in"], p["c_out"], p["H"]
+    g = torch.Generator().manual_seed(p["seed"])
+    if p["nn"] == "linear":
+        h = ea.double()
+    else:
+        h = torch.relu(ea.double() @ torch.randn(p["D"], H, generator=g, dtype=torch.float64)
+                       + torch.randn(H, generator=g, dtype=torch.float64))
+    hw = torch.randn(c_in * c_out, H, generator=g, dtype=torch.float64)
+    hb = torch.randn(c_in * c_out, generator=g, dtype=torch.float64) if p["head_bias"] else None
+    root = torch.randn(c_in, c_out, generator=g, dtype=torch.float64) if p["root"] else None
+    bias = torch.randn(c_out, generator=g, dtype=torch.float64) if p["bias"] else None
+    out = NR.nn_conv(x, ei, h, hw, hb, c_in, c_out, root, bias, p["aggr"], p["flow"])
+    scale = NR.nn_conv(x, ei, h, hw, hb, c_in, c_out, root, bias, p["aggr"], p["flow"], absolute=True)
+    assert tuple(out.shape) == (N, c_out)
+    _close64(out, NR.nn_conv_loop(x, ei, h, hw, hb, c_in, c_out, root, bias, p["aggr"], p["flow"]), scale, "loop")
+    i, j = (1, 0) if p["flow"] == "source_to_target" else (0, 1)
+    dst, src = ei[i], ei[j]
+    L = NR.head_matrix(hw, hb, c_in, c_out)
+    Z_ = NR.bins(dst, src, N, h, x)
+    assert tuple(Z_.shape) == (N, (H + 1) * c_in)
+    by_bins = Z_ @ L
+    by_gather = NR.gather(dst, src, N, h, x.double() @ NR.gather_matrix(L, H, c_in, c_out), c_out)
+    terms = NR.bins(dst, src, N, h.abs(), x.abs()) @ L.abs()
+    _close64(by_bins, by_gather, terms, "bins @ L against gather")
+    plain = NR.nn_conv(x, ei, h, hw, hb, c_in, c_out, None, None, "add", p["flow"])
+    _close64(by_bins, plain, terms, "bins @ L against the layer")
+    dz = torch.randn(N, (H + 1) * c_in, generator=g, dtype=torch.float64)
+    assert tuple(NR.edge_grad(dst, src, dz, x, H).shape) == (ei.shape[1], H)
+    if ei.shape[1] == 0:
+        assert float(Z_.abs().sum()) == 0.0 and float(by_gather.abs().sum()) == 0.0
+
+
+@pytest.mark.parametrize("k", range(len(Z.RGCN_PINNED)))
+def test_rgcn_restatements_agree_on_the_pinned_examples(k):
+    """rgcn_conv against its literal loop, and bins(x) @ V against gather(x @ L'),
+    featured and featureless (x = the identity), with att_grad's shape."""
+    p = Z.RGCN_PINNED[k]
+    ei, x, et, en = Z.rgcn_inputs(p)
+    N, c_out, n_rel, B = p["N"], p["c_out"], p["R"], p["B"]
+    c_in = N if x is None else p["c_in"]
+    g = torch.Generator().manual_seed(p["seed"])
+    basis = torch.randn(B, c_in, c_out, generator=g, dtype=torch.float64)
+    att = torch.randn(n_rel, B, generator=g, dtype=torch.float64)
+    root = torch.randn(c_in, c_out, generator=g, dtype=torch.float64) if p["root"] else None
+    bias = torch.randn(c_out, generator=g, dtype=torch.float64) if p["bias"] else None
+    out = RR.rgcn_conv(x, ei, et, en, basis, att, root, bias, p["flow"])
+    scale = RR.rgcn_conv(x, ei, et, en, basis, att, root, bias, p["flow"], absolute=True)
+    assert tuple(out.shape) == (N, c_out)
+    _close64(out, RR.rgcn_conv_loop(x, ei, et, en, basis, att, root, bias, p["flow"]), scale, "loop")
+    i, j = (1, 0) if p["flow"] == "source_to_target" else (0, 1)
+    dst, src = ei[i], ei[j]
+    xe = torch.eye(N, dtype=torch.float64) if x is None else x.double()
+    ena = None if en is None else en.abs()
+    Z_ = RR.bins(dst, src, N, et, en, att, xe)
+    assert tuple(Z_.shape) == (N, B, c_in)
+    by_bins = Z_.reshape(N, B * c_in) @ basis.view(B * c_in, c_out)
+    y = torch.einsum("nc,bcf->nbf", xe, basis)                         # x @ L', laid out [n, B, Cout]
+    by_gather = RR.gather(dst, src, N, et, en, att, y)
+    terms = RR.bins(dst, src, N, et, ena, att.abs(), xe.abs()).reshape(N, B * c_in) @ basis.abs().view(B * c_in, c_out)
+    _close64(by_bins, by_gather, terms, "bins @ V against gather")
+    _close64(by_bins, RR.rgcn_conv(x, ei, et, en, basis, att, None, None, p["flow"]), terms, "bins @ V against the layer")
+    if x is None:                                                      # the featureless layer gathers basis in place
+        _close64(RR.gather(dst, src, N, et, en, att, basis.permute(1, 0, 2)), by_gather, terms, "basis in place")
+    dZ = torch.randn(N, B, c_in, generator=g, dtype=torch.float64)
+    assert tuple(RR.att_grad(et, en, dst, src, dZ, xe, n_rel).shape) == (n_rel, B)
+    if ei.shape[1] == 0:
+        assert float(Z_.abs().sum()) == 0.0 and float(RR.att_grad(et, en, dst, src, dZ, xe, n_rel).abs().sum()) == 0.0
+
+
+def test_assert_bound_compares_shapes_of_empty_tensors():
+    for ref in (NR, RR):
+        ref.assert_bound(torch.empty(0, 3), torch.empty(0, 3, dtype=torch.float64), torch.empty(0, 3), "empty")
+        for got, want in ((torch.empty(0, 3), torch.empty(0, 4)), (torch.empty(0), torch.empty(0, 1)),
+                          (torch.zeros(2, 1), torch.zeros(2, 3))):
+            with pytest.raises(AssertionError, match="shapes"):
+                ref.assert_bound(got, want.double(), want.double(), "mismatch")
+        with pytest.raises(AssertionError, match="exceeds"):
+            ref.assert_bound(torch.tensor([float("nan")]), torch.zeros(1, dtype=torch.float64),
+                             torch.ones(1, dtype=torch.float64), "an unwritten entry")

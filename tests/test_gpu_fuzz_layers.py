@@ -827,6 +827,58 @@ def test_empty_graphs_through_every_layer():
     assert global_max_pool(torch.empty(0, 3, device=DEV), idx, size=2).shape == (2, 3)
 
 
+def test_empty_graphs_through_the_fused_conv_layers():
+    """The layers added after test_empty_graphs_through_every_layer -- NNConv with
+    an mlp and with a bare Linear edge network in both forced forms, RGCNConv
+    featured in both forms and featureless -- on N in {0, 5} nodes without
+    edges: the output is [N, F_out]; for N = 5 it and every gradient equal the
+    float64 restatement; the backward runs and d x has x's shape.  The
+    featureless RGCNConv runs at N = 5 only (in_channels = 0 is not a layer)."""
+    from tests import test_gpu_nnconv as TN, test_gpu_rgcn as TR
+    from torch_geometric.nn import NNConv, RGCNConv
+    ei = torch.empty(2, 0, dtype=torch.long)
+    et = torch.empty(0, dtype=torch.long)
+    torch.manual_seed(11)
+    for N in (0, 5):
+        g = torch.Generator().manual_seed(N)
+        x = torch.randn(N, 4, generator=g)
+        for head in ("mlp", "linear"):
+            for form in ("bins", "gather"):
+                nn = torch.nn.Linear(2, 12) if head == "linear" else \
+                    torch.nn.Sequential(torch.nn.Linear(2, 6), torch.nn.ReLU(), torch.nn.Linear(6, 12))
+                conv = NNConv(4, 3, nn, aggr="mean")
+                ea = torch.empty(0, 2)
+                what = "NNConv %s %s N=%d E=0" % (head, form, N)
+                if N:
+                    out, grads = TN.check_layer(conv, x, ei, ea, form, what, ea_grad=head == "linear")
+                    assert tuple(grads["x"].shape) == (N, 4)
+                    if head == "linear":
+                        assert tuple(grads["edge_attr"].shape) == (0, 2)
+                else:
+                    xd = x.to(DEV).requires_grad_(True)
+                    out = conv.to(DEV)(xd, ei.to(DEV), ea.to(DEV), form=form)
+                    out.sum().backward()
+                    assert xd.grad is not None and xd.grad.shape == xd.shape, what
+                assert tuple(out.shape) == (N, 3), what
+        for form in ("bins", "gather", None):
+            conv = RGCNConv(4, 3, 7, 2)
+            what = "RGCNConv %s N=%d E=0" % (form, N)
+            if N:
+                out, grads = TR._check_layer(conv, x, ei, et, None, form, what)
+                assert tuple(grads["x"].shape) == (N, 4)
+                assert float(grads["att"].abs().sum()) == 0.0 and float(grads["basis"].abs().sum()) == 0.0
+            else:
+                xd = x.to(DEV).requires_grad_(True)
+                out = conv.to(DEV)(xd, ei.to(DEV), et.to(DEV), **({} if form is None else {"form": form}))
+                out.sum().backward()
+                assert xd.grad is not None and xd.grad.shape == xd.shape, what
+                assert conv.att.grad is not None and float(conv.att.grad.abs().sum()) == 0.0
+            assert tuple(out.shape) == (N, 3), what
+    out, grads = TR._check_layer(RGCNConv(5, 3, 7, 2), None, ei, et, None, None, "RGCNConv featureless N=5 E=0")
+    assert tuple(out.shape) == (5, 3) and float(grads["att"].abs().sum()) == 0.0
+    assert tuple(grads["root"].shape) == (5, 3)
+
+
 @settings(**dict(_SETTINGS, max_examples=max(10, _N_EX // 2)))
 @given(N=st.integers(1, 150), deg=st.floats(0.0, 8.0), F=st.sampled_from([1, 3, 8, 64, 100]),
        layer=st.sampled_from(["plain_add", "plain_max", "gcn", "gat", "sage", "graph"]),

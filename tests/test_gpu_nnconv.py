@@ -54,12 +54,16 @@ def graph(edges):
 
 # 1. the three kernels ---------------------------------------------------------
 
-@pytest.mark.parametrize("H", [1, 25, 128])
-@pytest.mark.parametrize("C", [1, 5, 33, 64, 70])
-def test_kernels_against_float64(edges, graph, C, H):
-    """bins (Cin = C: the flat mapping below 32 columns, the column mapping from
-    32 on, two column tiles at 70), gather (F = C) and edge_grad (Cin = C), h
-    with ldh = H + 3, with and without row_scale and bias."""
+def _nan(*shape):
+    """An output to hand to a kernel: an entry it leaves unwritten fails every comparison."""
+    return torch.full(shape, float("nan"), device=DEV)
+
+
+def check_aggregates(edges, csr, n, C, H, first_empty_row):
+    """bins (Cin = C) and gather (F = C) on the graph `edges` ([2, E] on the CPU;
+    csr: its destination CSR on the device, n nodes, rows first_empty_row.. without
+    in-edges), h with ldh = H + 3, with and without row_scale and bias, into
+    NaN-filled outputs."""
     from mi355_mp import ops
     assert ops.nnconv_ok(H, C, C)
     E = edges.shape[1]
@@ -67,33 +71,56 @@ def test_kernels_against_float64(edges, graph, C, H):
     g = torch.Generator().manual_seed(C * 1000 + H)
     hw = torch.randn(E, H + 3, generator=g)
     h = hw[:, :H]
-    x = torch.randn(N, C, generator=g)
-    y = torch.randn(N, (H + 1) * C, generator=g)
-    dz = torch.randn(N, (H + 1) * C, generator=g)
+    x = torch.randn(n, C, generator=g)
+    y = torch.randn(n, (H + 1) * C, generator=g)
     bias = torch.randn(C, generator=g)
-    scale = torch.rand(N, generator=g) + 0.5
+    scale = torch.rand(n, generator=g) + 0.5
     hd = hw.to(DEV)[:, :H]
     assert hd.stride(0) == H + 3
-    csr = graph.dst
-    z_ref, z_abs = R.bins(dst, src, N, h, x), R.bins(dst, src, N, h.abs(), x.abs())
-    o_ref, o_abs = R.gather(dst, src, N, h, y, C), R.gather(dst, src, N, h.abs(), y.abs(), C)
+    z_ref, z_abs = R.bins(dst, src, n, h, x), R.bins(dst, src, n, h.abs(), x.abs())
+    o_ref, o_abs = R.gather(dst, src, n, h, y, C), R.gather(dst, src, n, h.abs(), y.abs(), C)
     for sc in (None, scale):
         scd = None if sc is None else sc.to(DEV)
         mul = 1.0 if sc is None else sc.double().view(-1, 1)
-        Z = ops.nnconv_bins(csr, hd, x.to(DEV), scd)
-        assert Z.shape == (N, (H + 1) * C)
+        Z = ops.nnconv_bins(csr, hd, x.to(DEV), scd, out=_nan(n, (H + 1) * C))
+        assert Z.shape == (n, (H + 1) * C)
         R.assert_bound(Z, z_ref * mul, z_abs * mul, "bins C=%d H=%d scale=%s" % (C, H, sc is not None))
-        assert float(Z[200:].abs().max()) == 0.0                       # rows without slots are zero
+        assert float(Z[first_empty_row:].abs().max()) == 0.0           # rows without slots are zero
+        assert torch.equal(ops.nnconv_bins(csr, hd, x.to(DEV), scd), Z)
         for bs in (None, bias):
             bd = None if bs is None else bs.to(DEV)
             add, add_abs = (0.0, 0.0) if bs is None else (bs.double(), bs.double().abs())
-            o = ops.nnconv_gather(csr, hd, y.to(DEV), C, scd, bd)
+            o = ops.nnconv_gather(csr, hd, y.to(DEV), C, scd, bd, out=_nan(n, C))
             R.assert_bound(o, o_ref * mul + add, o_abs * mul + add_abs,
                            "gather F=%d H=%d scale=%s bias=%s" % (C, H, sc is not None, bs is not None))
-    dh = ops.nnconv_edge_grad(edges[1].to(DEV), edges[0].to(DEV), dz.to(DEV), x.to(DEV), H)
+            if bs is None:
+                assert float(o[first_empty_row:].abs().max()) == 0.0
+            assert torch.equal(ops.nnconv_gather(csr, hd, y.to(DEV), C, scd, bd), o)
+
+
+def check_edge_grad(edges, n, C, H):
+    """edge_grad (Cin = C) on the graph `edges`, into a NaN-filled output."""
+    from mi355_mp import ops
+    E = edges.shape[1]
+    dst, src = edges[1], edges[0]
+    g = torch.Generator().manual_seed(C * 1000 + H + 500000)
+    x = torch.randn(n, C, generator=g)
+    dz = torch.randn(n, (H + 1) * C, generator=g)
+    dh = ops.nnconv_edge_grad(edges[1].to(DEV), edges[0].to(DEV), dz.to(DEV), x.to(DEV), H, out=_nan(E, H))
     assert dh.shape == (E, H)
     R.assert_bound(dh, R.edge_grad(dst, src, dz, x, H), R.edge_grad(dst, src, dz.abs(), x.abs(), H),
                    "edge_grad C=%d H=%d" % (C, H))
+    assert torch.equal(ops.nnconv_edge_grad(edges[1].to(DEV), edges[0].to(DEV), dz.to(DEV), x.to(DEV), H), dh)
+
+
+@pytest.mark.parametrize("H", [1, 25, 128])
+@pytest.mark.parametrize("C", [1, 5, 33, 64, 70])
+def test_kernels_against_float64(edges, graph, C, H):
+    """bins (Cin = C: the flat mapping below 32 columns, the column mapping from
+    32 on, two column tiles at 70), gather (F = C) and edge_grad (Cin = C), h
+    with ldh = H + 3, with and without row_scale and bias."""
+    check_aggregates(edges, graph.dst, N, C, H, 200)
+    check_edge_grad(edges, N, C, H)
 
 
 @pytest.mark.parametrize("C", [5, 33])
@@ -142,11 +169,12 @@ def _split(conv):
     return torch.nn.Sequential(*mods[:-1]), mods[-1]
 
 
-def _reference(conv, x, ei, ea, absolute=False, gout=None):
+def _reference(conv, x, ei, ea, absolute=False, gout=None, ea_grad=False):
     """The restatement on float64 copies of the layer's parameters; with gout
     its autograd too.  absolute: sum |terms| -- every leaf by its magnitude, the
     trunk's ReLU as the fixed mask of the signed computation.  Returns (out,
-    {name: grad}) with the layer's parameter names and 'x'."""
+    {name: grad}) with the layer's parameter names and 'x'; ea_grad (a bare
+    Linear nn, whose h is edge_attr itself): and 'edge_attr'."""
     trunk, head = _split(conv)
     cvt = (lambda t: t.detach().cpu().double().abs()) if absolute else (lambda t: t.detach().cpu().double())
     leaves = {n: cvt(p).requires_grad_(True) for n, p in conv.named_parameters()}
@@ -157,7 +185,10 @@ def _reference(conv, x, ei, ea, absolute=False, gout=None):
     ea = ea.view(-1, 1) if ea.dim() == 1 else ea
     if trunk is None:
         h = ea.abs() if absolute else ea
+        if ea_grad:
+            h = leaves["edge_attr"] = h.clone().requires_grad_(True)
     else:
+        assert not ea_grad
         assert len(trunk) == 2 and isinstance(trunk[1], torch.nn.ReLU)
         w1, b1 = trunk[0].weight.detach().cpu().double(), trunk[0].bias.detach().cpu().double()
         mask = ((ea @ w1.t() + b1) > 0).double()
@@ -169,6 +200,33 @@ def _reference(conv, x, ei, ea, absolute=False, gout=None):
         (out * (gout.double().abs() if absolute else gout.double())).sum().backward()
         grads = {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
     return out.detach(), grads
+
+
+def check_layer(conv, x, ei, ea, form, what, ea_grad=False, seed=5):
+    """Forward and every gradient (x, every parameter; ea_grad: edge_attr, a leaf
+    the edge-gradient kernel writes) of one layer call on any graph against the
+    restatement.  Returns (out, {name: grad}) of the device run."""
+    conv = conv.to(DEV)
+    n = x.shape[0]
+    gout = torch.randn(n, conv.out_channels, generator=torch.Generator().manual_seed(seed))
+    xd = x.to(DEV).requires_grad_(True)
+    ead = ea.to(DEV).requires_grad_(ea_grad)
+    out = conv(xd, ei.to(DEV), ead, form=form)
+    assert tuple(out.shape) == (n, conv.out_channels), what
+    (out * gout.to(DEV)).sum().backward()
+    ref, want = _reference(conv, x, ei, ea, gout=gout, ea_grad=ea_grad)
+    ref_abs, scale = _reference(conv, x, ei, ea, absolute=True, gout=gout, ea_grad=ea_grad)
+    R.assert_bound(out, ref, ref_abs, "forward " + what)
+    got = {name: p.grad for name, p in conv.named_parameters()}
+    got["x"] = xd.grad
+    if ea_grad:
+        got["edge_attr"] = ead.grad
+    assert sorted(got) == sorted(want), (sorted(got), sorted(want))
+    for name in sorted(got):
+        assert got[name] is not None, name
+        assert tuple(got[name].shape) == tuple(want[name].shape), name
+        R.assert_bound(got[name], want[name], scale[name], "grad %s %s" % (name, what))
+    return out, got
 
 
 @pytest.mark.parametrize("form", ["bins", "gather", None])

@@ -93,26 +93,30 @@ def graph(edges):
 
 # 1. the three kernels ---------------------------------------------------------
 
-@pytest.mark.parametrize("B", [1, 5, 30, 33])
-@pytest.mark.parametrize("C", [1, 5, 16, 33, 64, 70])
-def test_kernels_against_float64(edges, types, norm, graph, C, B):
-    """bins (C: the flat mapping below 32 columns, the column mapping from 32 on,
-    two column tiles at 70; B: one, part of one, two and three tiles of 16),
-    gather (F = C) and att_grad (both roles), for R in {1, 7, 46}, att with
-    ld_att = B + 2, with and without edge_norm, node-major and block-major."""
+def _nan(*shape):
+    """An output to hand to a kernel: an entry it leaves unwritten fails every comparison."""
+    return torch.full(shape, float("nan"), device=DEV)
+
+
+def check_kernels(edges, csr, n, types, norm, C, B, first_empty_row):
+    """bins, gather (F = C) and att_grad (both roles) on the graph `edges` ([2, E]
+    on the CPU; csr: its destination CSR on the device, n nodes, rows
+    first_empty_row.. without in-edges) for every {R: edge types} of `types`
+    (relation 1 without edges when R > 1), att with ld_att = B + 2, with and
+    without edge_norm, node-major and block-major, into NaN-filled outputs."""
     from mi355_mp import ops
     dst, src = edges[1], edges[0]
     dstd, srcd = edges[1].to(DEV), edges[0].to(DEV)
     g = torch.Generator().manual_seed(C * 1000 + B)
-    x = torch.randn(N, C, generator=g)
-    y = torch.randn(N, B, C, generator=g)
-    p = torch.randn(N, B, C, generator=g)
-    q = torch.randn(N, C, generator=g)
+    x = torch.randn(n, C, generator=g)
+    y = torch.randn(n, B, C, generator=g)
+    p = torch.randn(n, B, C, generator=g)
+    q = torch.randn(n, C, generator=g)
     bias = torch.randn(C, generator=g)
     xd, qd, bd = x.to(DEV), q.to(DEV), bias.to(DEV)
-    y_node, y_block = y.view(N, B * C).to(DEV), y.permute(1, 0, 2).contiguous().to(DEV)
-    p_node, p_block = p.view(N, B * C).to(DEV), p.permute(1, 0, 2).contiguous().to(DEV)
-    for n_rel in (1, 7, 46):
+    y_node, y_block = y.view(n, B * C).to(DEV), y.permute(1, 0, 2).contiguous().to(DEV)
+    p_node, p_block = p.view(n, B * C).to(DEV), p.permute(1, 0, 2).contiguous().to(DEV)
+    for n_rel in sorted(types):
         assert ops.rgcn_ok(n_rel, B, C, C)
         et = types[n_rel]
         etd = et.to(DEV)
@@ -124,31 +128,45 @@ def test_kernels_against_float64(edges, types, norm, graph, C, B):
         for en in (None, norm):
             tag = "C=%d B=%d R=%d norm=%s" % (C, B, n_rel, en is not None)
             end = None if en is None else en.to(DEV)
-            z_ref = R.bins(dst, src, N, et, en, att, x)
-            z_abs = R.bins(dst, src, N, et, en, att.abs(), x.abs())
-            Z = ops.rgcn_bins(graph.dst, etd, end, attd, xd)
-            assert Z.shape == (N, B * C)
-            R.assert_bound(Z, z_ref.view(N, B * C), z_abs.view(N, B * C), "bins " + tag)
-            assert float(Z[250:].abs().max()) == 0.0                  # rows without slots are zero
-            Zb = torch.empty(B, N, C, device=DEV)
-            ops.rgcn_bins(graph.dst, etd, end, attd, xd, out=Zb)      # through the block stride
-            assert torch.equal(Zb.permute(1, 0, 2).reshape(N, B * C), Z)
-            o_ref = R.gather(dst, src, N, et, en, att, y)
-            o_abs = R.gather(dst, src, N, et, en, att.abs(), y.abs())
-            o = ops.rgcn_gather(graph.dst, etd, end, attd, y_node, C)
+            z_ref = R.bins(dst, src, n, et, en, att, x)
+            z_abs = R.bins(dst, src, n, et, en, att.abs(), x.abs())
+            Z = ops.rgcn_bins(csr, etd, end, attd, xd, out=_nan(n, B * C))
+            assert Z.shape == (n, B * C)
+            R.assert_bound(Z, z_ref.view(n, B * C), z_abs.view(n, B * C), "bins " + tag)
+            assert float(Z[first_empty_row:].abs().max()) == 0.0      # rows without slots are zero
+            assert torch.equal(ops.rgcn_bins(csr, etd, end, attd, xd), Z)
+            Zb = _nan(B, n, C)
+            ops.rgcn_bins(csr, etd, end, attd, xd, out=Zb)            # through the block stride
+            assert torch.equal(Zb.permute(1, 0, 2).reshape(n, B * C), Z)
+            o_ref = R.gather(dst, src, n, et, en, att, y)
+            o_abs = R.gather(dst, src, n, et, en, att.abs(), y.abs())
+            o = ops.rgcn_gather(csr, etd, end, attd, y_node, C, out=_nan(n, C))
             R.assert_bound(o, o_ref, o_abs, "gather " + tag)
-            assert torch.equal(ops.rgcn_gather(graph.dst, etd, end, attd, y_block), o)
-            ob = ops.rgcn_gather(graph.dst, etd, end, attd, y_block, bias=bd)
+            assert float(o[first_empty_row:].abs().max()) == 0.0
+            assert torch.equal(ops.rgcn_gather(csr, etd, end, attd, y_node, C), o)
+            assert torch.equal(ops.rgcn_gather(csr, etd, end, attd, y_block, out=_nan(n, C)), o)
+            ob = ops.rgcn_gather(csr, etd, end, attd, y_block, bias=bd, out=_nan(n, C))
             R.assert_bound(ob, o_ref + bias.double(), o_abs + bias.double().abs(), "gather + bias " + tag)
-            # att grad: P = dZ [N, B*C] by destination with Q = x by source (the featured backward), and
-            # P = basis [B, N, C] in place by source with Q = g by destination (the featureless one)
+            # att grad: P = dZ [n, B*C] by destination with Q = x by source (the featured backward), and
+            # P = basis [B, n, C] in place by source with Q = g by destination (the featureless one)
             for rows, cols, rd, cd, pd in ((dst, src, dstd, srcd, p_node), (src, dst, srcd, dstd, p_block)):
-                da = ops.rgcn_att_grad(plan, rd, cd, end, pd, qd, B)
+                da = ops.rgcn_att_grad(plan, rd, cd, end, pd, qd, B, out=_nan(n_rel, B))
                 assert da.shape == (n_rel, B)
                 R.assert_bound(da, R.att_grad(et, en, rows, cols, p, q, n_rel),
                                R.att_grad(et, en, rows, cols, p.abs(), q.abs(), n_rel), "att_grad " + tag)
+                assert torch.equal(ops.rgcn_att_grad(plan, rd, cd, end, pd, qd, B), da)
                 if n_rel > 1:
                     assert float(da[1].abs().max()) == 0.0            # the relation without edges
+
+
+@pytest.mark.parametrize("B", [1, 5, 30, 33])
+@pytest.mark.parametrize("C", [1, 5, 16, 33, 64, 70])
+def test_kernels_against_float64(edges, types, norm, graph, C, B):
+    """bins (C: the flat mapping below 32 columns, the column mapping from 32 on,
+    two column tiles at 70; B: one, part of one, two and three tiles of 16),
+    gather (F = C) and att_grad (both roles), for R in {1, 7, 46}, att with
+    ld_att = B + 2, with and without edge_norm, node-major and block-major."""
+    check_kernels(edges, graph.dst, N, types, norm, C, B, 250)
 
 
 @pytest.mark.parametrize("C", [5, 33])
@@ -205,14 +223,16 @@ def _reference(conv, x, ei, et, en, absolute=False, gout=None):
 
 
 def _check_layer(conv, x, ei, et, en, form, what, en_grad=False):
-    """Forward and every gradient of one layer call against the restatement."""
+    """Forward and every gradient of one layer call on any graph against the
+    restatement.  Returns (out, {name: grad}) of the device run."""
     conv = conv.to(DEV)
-    gout = torch.randn(N, conv.out_channels, generator=torch.Generator().manual_seed(5))
+    n = conv.in_channels if x is None else x.shape[0]
+    gout = torch.randn(n, conv.out_channels, generator=torch.Generator().manual_seed(5))
     xd = None if x is None else x.to(DEV).requires_grad_(True)
     end = None if en is None else en.to(DEV).requires_grad_(en_grad)
     kw = {} if form is None else {"form": form}
     out = conv(xd, ei.to(DEV), et.to(DEV), end, **kw)
-    assert out.shape == (N, conv.out_channels)
+    assert out.shape == (n, conv.out_channels)
     (out * gout.to(DEV)).sum().backward()
     ref, want = _reference(conv, x, ei, et, en, gout=gout)
     ref_abs, scale = _reference(conv, x, ei, et, en, absolute=True, gout=gout)
@@ -227,7 +247,9 @@ def _check_layer(conv, x, ei, et, en, form, what, en_grad=False):
     assert sorted(got) == sorted(want), (sorted(got), sorted(want))
     for name in sorted(got):
         assert got[name] is not None, name
+        assert tuple(got[name].shape) == tuple(want[name].shape), name
         R.assert_bound(got[name], want[name], scale[name], "grad %s %s" % (name, what))
+    return out, got
 
 
 @pytest.mark.parametrize("root_bias", [True, False])

@@ -300,3 +300,52 @@ def test_nnconv_abi_rejections_under_asan():
     assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-2000:]
     m = re.match(r"abi_reject_nnconv: (\d+) cases, 0 failures", r.stdout.strip().splitlines()[-1])
     assert m and int(m.group(1)) >= 50, r.stdout[-2000:]
+
+
+# ---- which edge-gradient kernel a shape takes ------------------------------------------
+
+def _width_restated(H, c_in):
+    """The dispatch of nnconv_edge_grad, restated: the grouped kernel up to 32
+    columns; above, the lanes W of 32 or 64 that waste the fewest lanes and
+    values of h, ties to 64."""
+    if c_in <= 32:
+        return 0
+
+    def used(W):
+        return c_in / (-(-c_in // W) * W) * H / (-(-H // W) * W)
+    return 32 if used(32) > used(64) else 64
+
+
+def test_edge_grad_width_is_the_dispatch_restated(lib):
+    from mi355_mp import ops
+    seen = set()
+    for c_in in range(1, 201):
+        for H in range(1, 201):
+            w = lib.mp_nnconv_edge_grad_width(H, c_in)
+            assert w == _width_restated(H, c_in), (H, c_in, w)
+            seen.add(w)
+    assert seen == {0, 32, 64}
+    assert ops.nnconv_edge_grad_width(40, 70) == 32 and ops.nnconv_edge_grad_width(40, 33) == 64
+    assert ops.nnconv_edge_grad_width(128, 32) == 0
+    assert lib.mp_nnconv_edge_grad_width(0, 33) == -1 and "H = 0" in lib.mp_last_error().decode()
+    assert lib.mp_nnconv_edge_grad_width(5, 0) == -1 and lib.mp_nnconv_edge_grad_width(1024, 1024) == -1
+    with pytest.raises(ValueError, match="H = 0"):
+        ops.nnconv_edge_grad_width(0, 33)
+    from mi355_mp import _lib
+    assert _lib.SIGNATURES["mp_nnconv_edge_grad_width"][0] is _lib.i64
+    assert "mp_nnconv_edge_grad_width" not in _lib.STATUS_RETURNING
+
+
+def test_the_lane_shape_sweep_reaches_every_edge_grad_tile_shape(lib):
+    """The coverage the GPU sweep (tests/test_gpu_conv_lane_shapes.py) claims, by the
+    library's own dispatch: checked here too, where there is no GPU."""
+    from tests import _conv_lane_cases as K
+    width = lambda H, c_in: lib.mp_nnconv_edge_grad_width(H, c_in)     # noqa: E731
+    assert K.edge_grad_reach(width, K.NNCONV_WIDTHS + K.NNCONV_EDGE_GRAD) >= K.EDGE_GRAD_REACHED
+    assert K.edge_grad_reach(width, K.NNCONV_WIDTHS) == {"grouped", "w32 single partial tile", "w32 several c per lane"}
+    for case, (w, tiles, last) in zip(K.NNCONV_EDGE_GRAD, ((64, 1, 40), (64, 1, 63), (64, 2, 36), (32, 2, 8),
+                                                           (32, 3, 1), (64, 1, 33), (32, 1, 5))):
+        c_in, H = case
+        assert (width(H, c_in), -(-H // w), H - (-(-H // w) - 1) * w) == (w, tiles, last), case
+    K.tiny_graph()
+    assert torch.bincount(K.tiny_relations(3), minlength=3)[1] == 0
