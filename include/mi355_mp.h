@@ -879,6 +879,82 @@ int64_t mp_rgcn_att_grad_f32(const int64_t* perm, const int64_t* relptr, const i
                              int64_t ldp_block, const float* Q, int64_t ldq, int32_t R, int32_t B, int32_t C,
                              float* datt, int64_t ld_datt, size_t datt_bytes, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- DNAConv: per-edge attention over layer histories (csrc/mp_dna.hip)
+ * PyG 1.4.3's nn.conv.DNAConv [U] gathers x_j as [E, T, C] and projects keys and
+ * values per edge.  The projections depend on the node only, so the caller runs
+ * them once per node: Q = lin_q(x[:, T-1]) [n, C], K = lin_k(x), V = lin_v(x)
+ * [n, T, C].  Per edge e = (j -> i) and head h (d = C / H channels) what is left is
+ *   s_t = <Q_i[h], K_j[t][h]> / sqrt(d)
+ *   a_t = exp(s_t - m) / (sum_u exp(s_u - m) + exp(-m)),  m = max(0, max_t s_t)
+ *   out_i[h] = sum_{e -> i} norm_e sum_t keep_t scale a_t V_j[t][h]
+ * the restricted softmax (margin 0) = the softmax over {0, s_1 .. s_T} without its
+ * first entry; lse = m + log(sum_u exp(s_u - m) + exp(-m)) gives a_t = exp(s_t - lse).
+ * Rows: q, out, gout, dq [., ld >= C]; k, v, dk, dv [., ld >= T * C] with entry (t, c)
+ * of a row at t * C + c (any ld >= T * C: K and V may be two arrays, or the halves
+ * of one fused projection [n, 2, T, C] passed as two pointers with ld = 2 * T * C,
+ * each with the bytes from its own pointer on).  Every array travels with its extent in bytes, checked before
+ * any launch.  norm [n_norm] fp32 in ORIGINAL edge order (read through g->eid), or
+ * NULL = 1; n_norm must cover g's edge-id space (g->n_ids, or g->n_edges).  lse
+ * [ids, H] in edge-id order.
+ * Limits (mp_dna_ok != 0): T, H, C >= 1, C % H == 0, C / H <= 256, T * ceil((C / H)
+ * / 64) <= 48 (the source backward keeps 4 * T * ceil(d / 64) floats per lane in
+ * LDS: at most 48 KiB per wave) and T * C <= 2^20.  mp_dna_max_layers(H, C): the
+ * largest T inside them, 0 when no T is.
+ * One lane group (min(64, pow2 >= d) lanes) owns a unit, visits its slots in slot
+ * order and adds left to right: fp32, deterministic, no atomics; all three kernels
+ * share the mapping, so a recomputed score has the forward's bits.  On a CSR whose
+ * schedule has g->chunk >= mp_dna_split_chunk() (64) a unit is (task, head): it
+ * walks the task's slots as the engine's main kernel does, a row cut by a task
+ * boundary leaves its partial sums in a slab (slot 2 * task: a continuation, 2 *
+ * task + 1: a head) and a fix-up launch adds each split row's partials in task
+ * order (g->wave_row, wave_slot, split_waves: the engine's sum fix-up protocol), so
+ * a hub row is walked by many tasks at once.  On a smaller schedule, or with
+ * g->wave_row NULL, a unit is (row, head) and walks the whole row, however long;
+ * no slab is used (mi355_mp's DNAConv builds its graphs with chunk >= 64).  ws: mp_dna_workspace(g, slot_floats) bytes, slot_floats = C for the
+ * forward and the destination backward, 2 * T * C for the source backward (d K |
+ * d V); one layout (csrc/mp_dna.hip DnaWs), required (and its extent checked)
+ * exactly when the kernels walk tasks.  Every entry of every output row is written
+ * exactly once (zeros for rows without slots), padding is left untouched.
+ *   mp_dna_aggregate_f32 (g: destination CSR; q, out by row, k, v by column):
+ *     out as above; lse NULL or written for every slot's edge id.
+ *   mp_dna_backward_dst_f32 (same CSR): with do = norm_e gout_i[h], dalpha_t = keep_t
+ *     scale <do, V_j[t][h]>, ds_t = a_t (dalpha_t - sum_u a_u dalpha_u):
+ *     dq_i[h] = sum_{e -> i} sum_t ds_t K_j[t][h] / sqrt(d); two sweeps over t.
+ *   mp_dna_backward_src_f32 (g: the source-keyed CSR; k, v, dk, dv by row, q, gout by
+ *     column): dv_j[t][h] = sum_e keep_t scale a_t do, dk_j[t][h] = sum_e ds_t Q_i[h] /
+ *     sqrt(d).
+ * Attention dropout: p_drop = 0 is none, else 0 < p_drop < 1 and keep_t =
+ * hash(seed, (eid * H + h) * T + t) >= floor(p * 2^32), scale = 1 / (1 - p): the
+ * draw of mp_gat_dropout_keep under another key.  mp_dna_dropout_keep writes keep
+ * [n_edges * H * T] bytes (0 / 1) in edge-id order.
+ * Additions to ABI 7 that return int64_t like the RGCN calls: the launches
+ * enqueued, >= 0, or -(MP_ERR_* code) with the reason in mp_last_error() -- for a
+ * bad argument (-MP_ERR_ARG), before any launch.  mp_dna_ok, mp_dna_max_layers,
+ * mp_dna_split_chunk and mp_dna_workspace answer a question and need no GPU. */
+int64_t mp_dna_ok(int32_t T, int32_t H, int32_t C);
+int64_t mp_dna_max_layers(int32_t H, int32_t C);
+int64_t mp_dna_split_chunk(void);
+size_t mp_dna_workspace(const mp_csr* g, int64_t slot_floats);
+int64_t mp_dna_aggregate_f32(const mp_csr* g, const float* q, int64_t ldq, size_t q_bytes, const float* k, int64_t ldk,
+                             size_t k_bytes, const float* v, int64_t ldv, size_t v_bytes, const float* norm,
+                             int64_t n_norm, int32_t T, int32_t H, int32_t C, uint64_t seed, float p_drop, float* out,
+                             int64_t ldo, size_t out_bytes, float* lse, size_t lse_bytes, void* ws, size_t ws_bytes,
+                             void* stream);
+int64_t mp_dna_backward_dst_f32(const mp_csr* g, const float* q, int64_t ldq, size_t q_bytes, const float* k,
+                                int64_t ldk, size_t k_bytes, const float* v, int64_t ldv, size_t v_bytes,
+                                const float* norm, int64_t n_norm, const float* gout, int64_t ldg, size_t g_bytes,
+                                const float* lse, size_t lse_bytes, int32_t T, int32_t H, int32_t C, uint64_t seed,
+                                float p_drop, float* dq, int64_t lddq, size_t dq_bytes, void* ws, size_t ws_bytes,
+                                void* stream);
+int64_t mp_dna_backward_src_f32(const mp_csr* g, const float* q, int64_t ldq, size_t q_bytes, const float* k,
+                                int64_t ldk, size_t k_bytes, const float* v, int64_t ldv, size_t v_bytes,
+                                const float* norm, int64_t n_norm, const float* gout, int64_t ldg, size_t g_bytes,
+                                const float* lse, size_t lse_bytes, int32_t T, int32_t H, int32_t C, uint64_t seed,
+                                float p_drop, float* dk, int64_t lddk, size_t dk_bytes, float* dv, int64_t lddv,
+                                size_t dv_bytes, void* ws, size_t ws_bytes, void* stream);
+int64_t mp_dna_dropout_keep(uint64_t seed, float p_drop, int32_t H, int32_t T, int64_t n_edges, uint8_t* keep,
+                            size_t keep_bytes, void* stream);
+
 /* ---- TopKPooling: score, per-graph select, gate, filter_adj (csrc/mp_pool.hip)
  * PyG 1.4.3 nn.pool.topk_pool [U] as one deterministic native path: no atomics
  * on values (two integer counters and one integer maximum aside), no dense

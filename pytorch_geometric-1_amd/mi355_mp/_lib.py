@@ -230,6 +230,19 @@ SIGNATURES = {
     "mp_rgcn_att_grad_workspace": (sz, [i64, i32, i32]),
     "mp_rgcn_att_grad_f32": (i64, [c_p, c_p, c_p, c_p, i64, c_p, c_p, i64, i64, c_p, i64, i32, i32, i32, c_p, i64, sz,
                                    c_p, sz, c_p]),
+    # DNAConv (csrc/mp_dna.hip): int64 returns again, the sign tested by ops._count_call
+    "mp_dna_ok": (i64, [i32, i32, i32]),           # an answer (0 or 1), not a status
+    "mp_dna_max_layers": (i64, [i32, i32]),        # the largest fused T of an (H, C) pair, 0 = none
+    "mp_dna_split_chunk": (i64, []),               # the schedule's task size from which the kernels walk tasks
+    "mp_dna_workspace": (sz, [ctypes.POINTER(MpCsr), i64]),
+    "mp_dna_aggregate_f32": (i64, [ctypes.POINTER(MpCsr), c_p, i64, sz, c_p, i64, sz, c_p, i64, sz, c_p, i64, i32, i32,
+                                   i32, u64, f32, c_p, i64, sz, c_p, sz, c_p, sz, c_p]),
+    "mp_dna_backward_dst_f32": (i64, [ctypes.POINTER(MpCsr), c_p, i64, sz, c_p, i64, sz, c_p, i64, sz, c_p, i64, c_p,
+                                      i64, sz, c_p, sz, i32, i32, i32, u64, f32, c_p, i64, sz, c_p, sz, c_p]),
+    "mp_dna_backward_src_f32": (i64, [ctypes.POINTER(MpCsr), c_p, i64, sz, c_p, i64, sz, c_p, i64, sz, c_p, i64, c_p,
+                                      i64, sz, c_p, sz, i32, i32, i32, u64, f32, c_p, i64, sz, c_p, i64, sz, c_p, sz,
+                                      c_p]),
+    "mp_dna_dropout_keep": (i64, [u64, f32, i32, i32, i64, c_p, sz, c_p]),
 }
 
 # Of the symbols declared `int` / `int32_t`, these answer a question (a version,

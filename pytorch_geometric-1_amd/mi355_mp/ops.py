@@ -1973,6 +1973,215 @@ def rgcn_propagate(graph, x, edge_type, edge_norm, att, basis, root=None, bias=N
 
 
 # ---------------------------------------------------------------------------
+# DNAConv: per-edge attention over layer histories (csrc/mp_dna.hip)
+# ---------------------------------------------------------------------------
+
+def dna_ok(T, H, C):
+    """Whether (T, H, C) lies inside the fused path's limits (mp_dna_ok)."""
+    return bool(_lib.native().mp_dna_ok(int(T), int(H), int(C)))
+
+
+def dna_max_layers(H, C):
+    """The largest history length T the fused path takes for (heads, channels)
+    (mp_dna_max_layers; 0 when it takes none; needs no GPU)."""
+    return int(_lib.native().mp_dna_max_layers(int(H), int(C)))
+
+
+def _dna_hist(t, what):
+    """A [n, T, C] operand addressed in place: entry (t, c) of a row at t*C + c, any
+    row stride >= T*C (a half of one fused K|V projection included)."""
+    if t.dtype != torch.float32 or t.dim() != 3:
+        raise TypeError("mi355_mp: %s must be float32 [n, T, C] (got %s %s)" % (what, t.dtype, tuple(t.shape)))
+    n, T, C = t.shape
+    if n and (t.stride(2) != 1 or t.stride(1) != C or t.stride(0) < T * C):
+        t = t.contiguous()
+    return t
+
+
+def _dna_args(csr, q, k, v, norm, heads):
+    q, k, v = _nnconv_rows(q, "q"), _dna_hist(k, "k"), _dna_hist(v, "v")
+    n, T, C = k.shape
+    if tuple(v.shape) != (n, T, C) or q.shape[1] != C:
+        raise ValueError("mi355_mp: q %s, k %s and v %s disagree" % (tuple(q.shape), tuple(k.shape), tuple(v.shape)))
+    if norm is not None:
+        if norm.dtype != torch.float32 or norm.dim() != 1:
+            raise ValueError("mi355_mp: norm must be float32 [E] (got %s %s)" % (norm.dtype, tuple(norm.shape)))
+        norm = norm.detach().contiguous()
+    keep = (q, k, v, norm)
+    args = (csr.struct("other"), q.data_ptr(), q.stride(0), _extent_bytes(q), k.data_ptr(), k.stride(0),
+            _extent_bytes(k), v.data_ptr(), v.stride(0), _extent_bytes(v), _lib.ptr(norm),
+            0 if norm is None else norm.numel())
+    return keep, args, (T, int(heads), C)
+
+
+def dna_split_chunk():
+    """The schedule task size from which the DNA kernels walk tasks and split long
+    rows (mp_dna_split_chunk; needs no GPU)."""
+    return int(_lib.native().mp_dna_split_chunk())
+
+
+def dna_target_tasks(n_rows, n_edges):
+    """graph_for's target_tasks for a DNA layer: the schedule gets tasks of
+    max(dna_split_chunk(), the default chunk) units, so the kernels walk tasks and
+    split long rows on a graph of any size (None: the default schedule has such
+    tasks already, and the layer shares the graph other layers build)."""
+    from .graph import auto_chunk
+    want = dna_split_chunk()
+    if auto_chunk(n_rows, n_edges) >= want:
+        return None
+    return max((int(n_rows) + int(n_edges)) // want, 1)
+
+
+def _dna_ws(nat, csr, slot_floats, dev):
+    """(keep-alive tensor, pointer, bytes) of one call's slab (mp_dna_workspace);
+    (None, None, 0) for a CSR the kernels walk by rows, which takes none."""
+    n = nat.mp_dna_workspace(csr.struct("other"), int(slot_floats))
+    if n <= nat.mp_dna_workspace(None, int(slot_floats)):      # the layout's minimum: no slab
+        return None, None, 0
+    ws = torch.empty(n, dtype=torch.uint8, device=dev)
+    return ws, ws.data_ptr(), n
+
+
+def _dna_drop(p, seed):
+    p = float(p)
+    return (int(seed or 0) & 0xFFFFFFFFFFFFFFFF, p)
+
+
+def dna_aggregate(csr, q, k, v, norm, heads, p=0.0, seed=0, out=None, want_lse=False):
+    """out[i, h] = sum over the slots (j -> i) of row i of norm[eid] * sum_t a_t v[j, t, h],
+    a = the restricted softmax over t of <q[i, h], k[j, t, h]> / sqrt(d), after
+    attention dropout (p, seed) when p > 0 (mp_dna_aggregate_f32).  q [n_rows, C],
+    k, v [n_cols, T, C], norm fp32 [E] in edge order or None.  Returns out, or
+    (out, lse [E, H]) with want_lse.  No autograd."""
+    nat = _lib.native()
+    keep, args, (T, H, C) = _dna_args(csr, q, k, v, norm, heads)
+    dev = keep[0].device
+    if out is None:
+        out = torch.empty((csr.n_rows, C), dtype=torch.float32, device=dev)
+    n_ids = max(int(getattr(csr, "n_ids", 0) or 0), csr.n_edges)
+    lse = torch.empty((n_ids, H), dtype=torch.float32, device=dev) if want_lse else None
+    ws, ws_ptr, ws_bytes = _dna_ws(nat, csr, C, dev)
+    _count_call(nat, "mp_dna_aggregate_f32", *args, T, H, C, *_dna_drop(p, seed), out.data_ptr(), out.stride(0),
+                _extent_bytes(out), _lib.ptr(lse), _lib.nbytes(lse), ws_ptr, ws_bytes, _lib.stream_ptr(dev))
+    return (out, lse) if want_lse else out
+
+
+def dna_backward_dst(csr, q, k, v, norm, gout, lse, heads, p=0.0, seed=0, out=None):
+    """d q [n_rows, C] of dna_aggregate over the same destination CSR, a recomputed
+    from lse (mp_dna_backward_dst_f32).  No autograd."""
+    nat = _lib.native()
+    keep, args, (T, H, C) = _dna_args(csr, q, k, v, norm, heads)
+    gout = _nnconv_rows(gout, "gout")
+    dev = gout.device
+    if out is None:
+        out = torch.empty((csr.n_rows, C), dtype=torch.float32, device=dev)
+    ws, ws_ptr, ws_bytes = _dna_ws(nat, csr, C, dev)
+    _count_call(nat, "mp_dna_backward_dst_f32", *args, gout.data_ptr(), gout.stride(0), _extent_bytes(gout),
+                lse.data_ptr(), _lib.nbytes(lse), T, H, C, *_dna_drop(p, seed), out.data_ptr(), out.stride(0),
+                _extent_bytes(out), ws_ptr, ws_bytes, _lib.stream_ptr(dev))
+    return out
+
+
+def dna_backward_src(csr, q, k, v, norm, gout, lse, heads, p=0.0, seed=0, dk=None, dv=None):
+    """(d k, d v) [n_rows, T, C] of dna_aggregate over the SOURCE-keyed CSR (rows =
+    sources: k, v; columns = destinations: q, gout) (mp_dna_backward_src_f32).
+    No autograd."""
+    nat = _lib.native()
+    keep, args, (T, H, C) = _dna_args(csr, q, k, v, norm, heads)
+    gout = _nnconv_rows(gout, "gout")
+    dev = gout.device
+    if dk is None:
+        dk = torch.empty((csr.n_rows, T, C), dtype=torch.float32, device=dev)
+    if dv is None:
+        dv = torch.empty((csr.n_rows, T, C), dtype=torch.float32, device=dev)
+    for t, what in ((dk, "dk"), (dv, "dv")):
+        if t.dtype != torch.float32 or tuple(t.shape) != (csr.n_rows, T, C) or \
+                (t.numel() and (t.stride(2) != 1 or t.stride(1) != C or t.stride(0) < T * C)):
+            raise ValueError("mi355_mp: %s must be float32 [%d, %d, %d] with rows of T*C floats" % (what, csr.n_rows, T, C))
+    ws, ws_ptr, ws_bytes = _dna_ws(nat, csr, 2 * T * C, dev)
+    _count_call(nat, "mp_dna_backward_src_f32", *args, gout.data_ptr(), gout.stride(0), _extent_bytes(gout),
+                lse.data_ptr(), _lib.nbytes(lse), T, H, C, *_dna_drop(p, seed), dk.data_ptr(), dk.stride(0),
+                _extent_bytes(dk), dv.data_ptr(), dv.stride(0), _extent_bytes(dv), ws_ptr, ws_bytes,
+                _lib.stream_ptr(dev))
+    return dk, dv
+
+
+def dna_dropout_keep(graph, seed, p, H, T):
+    """The attention-dropout keep mask [E, H, T] (bool, the graph's edge order) that
+    the fused DNA kernels apply for (seed, p) (mp_dna_dropout_keep)."""
+    nat = _lib.native()
+    csr = graph.dst
+    E = csr.n_edges
+    dev = csr.rowptr.device
+    keep = torch.empty((E, int(H), int(T)), dtype=torch.uint8, device=dev)
+    _count_call(nat, "mp_dna_dropout_keep", int(seed) & 0xFFFFFFFFFFFFFFFF, float(p), int(H), int(T), E,
+                _lib.ptr(keep) if keep.numel() else None, _lib.nbytes(keep), _lib.stream_ptr(dev))
+    return keep.bool()
+
+
+class _DNAPropagate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, graph, norm, heads, p, seed):
+        train = any(ctx.needs_input_grad[:3])
+        res = dna_aggregate(graph.dst, q, k, v, norm, heads, p, seed, want_lse=train)
+        out, lse = res if train else (res, None)
+        ctx.graph, ctx.heads, ctx.p, ctx.seed = graph, heads, p, seed
+        # the cached Graph holds its edge_index weakly and builds the transposed CSR
+        # on first use, in backward: keep the tensor alive until then
+        ctx.save_for_backward(q, k, v, norm, lse, graph._edge_index())
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        q, k, v, norm, lse, _ = ctx.saved_tensors
+        graph = ctx.graph
+        g = g.contiguous()
+        gq = gk = gv = None
+        if ctx.needs_input_grad[0]:
+            gq = dna_backward_dst(graph.dst, q, k, v, norm, g, lse, ctx.heads, ctx.p, ctx.seed)
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            gk, gv = dna_backward_src(graph.src, q, k, v, norm, g, lse, ctx.heads, ctx.p, ctx.seed)
+            gk = gk if ctx.needs_input_grad[1] else None
+            gv = gv if ctx.needs_input_grad[2] else None
+        return gq, gk, gv, None, None, None, None, None
+
+
+def dna_propagate(graph, q, k, v, norm, heads, p=0.0, seed=None):
+    """out[i] = sum_{e = (j -> i)} norm[e] * attention(q[i], k[j], v[j]) per head
+
+    DNAConv's propagate on node-level projections: q [N, C] = lin_q(x[:, -1]),
+    k, v [N, T, C] = lin_k(x), lin_v(x) (two tensors, or the halves of one fused
+    projection); one query per destination attends over the T keys of every
+    in-neighbour under the restricted softmax (margin 0), the messages are scaled
+    by norm (fp32 [E], no gradient, or None) and summed.  No [E, T, C] array is
+    built; the only per-edge float array is lse [E, H], kept for the backward.
+    p in (0, 1): attention dropout with the hash mask of dna_dropout_keep(graph,
+    seed, p, heads, T); seed None draws one (dropout_seed).  Deterministic, native
+    forward and backward: d q over the destination CSR, d k and d v over the
+    source-keyed one; a launch is skipped when nothing needs its gradient."""
+    _lib.require_device(q, k, v, norm)
+    if k.dim() != 3 or q.dim() != 2:
+        raise ValueError("mi355_mp: q must be [N, C] and k, v [N, T, C] (got %s, %s)" % (tuple(q.shape), tuple(k.shape)))
+    n, T, C = k.shape
+    heads, p = int(heads), float(p)
+    if norm is not None and norm.requires_grad:
+        raise NotImplementedError("mi355_mp: dna_propagate has no gradient with respect to norm")
+    if not 0.0 <= p < 1.0:
+        raise ValueError("mi355_mp: attention dropout p must lie in [0, 1) (got %r)" % (p,))
+    if heads < 1 or C % heads != 0 or not dna_ok(T, heads, C):
+        raise NotImplementedError("mi355_mp: outside the fused DNA path's limits: T = %d, heads = %d, channels = %d "
+                                  "(largest T: %d)" % (T, heads, C, dna_max_layers(heads, C) if heads >= 1 else 0))
+    if n != graph.n_src or n != graph.n_dst or q.shape[0] != n:
+        raise ValueError("mi355_mp: %d nodes (q %d), the graph %d sources and %d destinations"
+                         % (n, q.shape[0], graph.n_src, graph.n_dst))
+    if norm is not None and norm.numel() != graph.dst.n_edges:
+        raise ValueError("mi355_mp: norm has %d entries, the graph %d edges" % (norm.numel(), graph.dst.n_edges))
+    if p > 0.0 and seed is None:
+        seed = dropout_seed(q.device)
+    return _DNAPropagate.apply(q, k, v, graph, norm, heads, p, 0 if p == 0.0 else int(seed))
+
+
+# ---------------------------------------------------------------------------
 # TopKPooling (PyG 1.4.3 nn.pool.topk_pool [U]; csrc/mp_pool.hip)
 # ---------------------------------------------------------------------------
 

@@ -1,5 +1,5 @@
 from .conv import MessagePassing, GCNConv, GATConv, SAGEConv, GraphConv, ChebConv, AGNNConv, SGConv, GINConv, SplineConv
-from .conv import PointConv, NNConv, RGCNConv
+from .conv import PointConv, NNConv, RGCNConv, DNAConv
 from .glob import global_add_pool, global_mean_pool, global_max_pool, Set2Set, GlobalAttention
 from .pool import (TopKPooling, voxel_grid, consecutive_cluster, max_pool, max_pool_x, avg_pool, avg_pool_x, pool_edge,
                    pool_batch, pool_pos, graclus, fps, radius, radius_graph)
@@ -10,4 +10,4 @@ __all__ = ["MessagePassing", "GCNConv", "GATConv", "SAGEConv", "GraphConv", "Che
            "GINConv", "SplineConv", "global_add_pool", "global_mean_pool", "global_max_pool", "TopKPooling",
            "voxel_grid", "consecutive_cluster", "max_pool", "max_pool_x", "avg_pool", "avg_pool_x", "pool_edge",
            "pool_batch", "pool_pos", "graclus", "fps", "radius", "radius_graph", "PointConv", "NNConv", "Set2Set",
-           "GlobalAttention", "DataParallel", "RGCNConv"]
+           "GlobalAttention", "DataParallel", "RGCNConv", "DNAConv"]

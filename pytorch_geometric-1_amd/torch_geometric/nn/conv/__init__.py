@@ -11,6 +11,7 @@ from .spline_conv import SplineConv
 from .point_conv import PointConv
 from .nn_conv import NNConv
 from .rgcn_conv import RGCNConv
+from .dna_conv import DNAConv
 
 __all__ = ["MessagePassing", "GCNConv", "GATConv", "SAGEConv", "GraphConv", "ChebConv", "AGNNConv", "SGConv", "GINConv",
-           "SplineConv", "PointConv", "NNConv", "RGCNConv"]
+           "SplineConv", "PointConv", "NNConv", "RGCNConv", "DNAConv"]

@@ -8,6 +8,12 @@ def uniform(size, tensor):
         tensor.data.uniform_(-bound, bound)
 
 
+def kaiming_uniform(tensor, fan, a):
+    bound = math.sqrt(6 / ((1 + a ** 2) * fan))
+    if tensor is not None:
+        tensor.data.uniform_(-bound, bound)
+
+
 def glorot(tensor):
     if tensor is not None:
         stdv = math.sqrt(6.0 / (tensor.size(-2) + tensor.size(-1)))
