@@ -1273,6 +1273,65 @@ int64_t mp_point_edge_features_f32(const float* x_src, int64_t ldx, int32_t F, c
                                const int64_t* src, const int64_t* dst, int64_t n_edges, float* out, int64_t ldo,
                                size_t out_bytes, void* stream);
 
+/* ---- Nearest neighbours: knn, knn_graph, nearest, knn_interpolate (csrc/mp_knn.hip) ----
+ * The nearest-neighbour half of torch_cluster 1.5 / PyG 1.4.3 (nn.knn, nn.knn_graph,
+ * nn.nearest, nn.unpool.knn_interpolate [U]) as pure functions of their inputs;
+ * tests/_knn_ref.py restates them in numpy.  Upstream leaves the order of equal
+ * distances to the hardware; here it is defined.  No float is added atomically,
+ * there is no CPU path, and every index read from device memory is bounded before
+ * it is used.  The entry points are additions: the ABI version is unchanged.
+ *
+ * Squared distance: the one of "Point sets" with the width lifted.  D = 1 ..
+ * MP_KNN_MAX_D columns (a build knob, default 256; mp_knn_max_d()), fp32, every
+ * operation rounded, nothing contracted, left to right:
+ *     acc = (a_0 - b_0) * (a_0 - b_0);  acc = acc + (a_d - b_d) * (a_d - b_d), d = 1..D-1
+ * x and y may have a row stride (ldx, ldy >= D).
+ *
+ * mp_knn_search_f32: for every row j of y, of the rows i of x in the same graph
+ *   (batch_y [n_y] int64 or NULL = graph 0; graph g searches rows [starts_x[g],
+ *   starts_x[g + 1]) of x, a g outside [0, n_graphs_x) finds nothing) the
+ *   min(k, n_g) smallest under the key (d2(x_i, y_j), i): equal distances go to
+ *   the lower index.  d2 >= +0, so (bits(d2) << 32) | in-graph index orders as an
+ *   unsigned 64-bit integer; that word is what the kernel compares.  Non-finite
+ *   coordinates never fault and never select outside the query's graph; what they
+ *   select is unspecified.  1 <= k <= 64 (mp_knn_max_k(): one slot per lane).
+ *   One wave per query; lane l holds the l-th smallest key so far, a candidate
+ *   below the k-th key is inserted by a wave shift.  mp_knn_path(D): 0 = query and
+ *   candidates in registers (D <= 8, a template; a workgroup whose four queries
+ *   search the same rows stages its candidates in LDS), 1 = the general width
+ *   (the query row in LDS), or -MP_ERR_ARG for a D outside [1, MP_KNN_MAX_D].
+ *   The selection goes to a slab of the workspace (mp_knn_workspace(n_y, k) bytes;
+ *   n_y * k < 2^31): per query k rows of x as int32, their d2, and a count, in
+ *   ascending key.  The counts are scanned; counts[0] = E (int64[4], device).
+ *
+ * mp_knn_fill: compacts the slab to out_y / out_x [E] int64, sorted by y and
+ *   within a y ascending in the key.  out_w (or NULL) [E] float: the pair's
+ *   normalised interpolation weight w_t / W_j (below).
+ *
+ * mp_knn_interpolate_f32: out[j, :] = (sum_t w_t * x[i_t, :]) / (sum_t w_t) over the
+ *   slab's entries i_0 .. i_{c-1} of row j, w_t = 1 / max(d2_t, 1e-16f), both sums in
+ *   the order t = 0 .. c-1 in fp32, every operation rounded; a row with c = 0 is
+ *   zeros.  It needs no E and no host read.  A lane group per row; float4 loads
+ *   when x and out are 16-byte aligned with C, ldx and ldo multiples of 4.
+ *
+ * mp_knn_search_f32, mp_knn_fill and mp_knn_interpolate_f32 return int64_t, not a
+ * status: the launches enqueued, >= 0, or -(MP_ERR_* code) with the reason in
+ * mp_last_error() when the call is refused -- for a bad argument, before any
+ * launch.  They are not among the `int` status symbols a binding may wrap to
+ * raise: the caller tests the sign itself.  mp_knn_path, mp_knn_max_k and
+ * mp_knn_max_d answer a question. */
+int64_t mp_knn_max_k(void);
+int64_t mp_knn_max_d(void);
+int64_t mp_knn_path(int32_t D);
+size_t mp_knn_workspace(int64_t n_y, int64_t k);
+int64_t mp_knn_search_f32(const float* x, int64_t ldx, int64_t n_x, const float* y, int64_t ldy, int64_t n_y, int32_t D,
+                          const int64_t* batch_y, const int64_t* starts_x, int64_t n_graphs_x, int64_t k,
+                          int64_t* counts, size_t counts_bytes, void* ws, size_t ws_bytes, void* stream);
+int64_t mp_knn_fill(int64_t n_y, int64_t k, int64_t n_edges, int64_t* out_y, int64_t* out_x, size_t out_bytes,
+                    float* out_w, size_t out_w_bytes, void* ws, size_t ws_bytes, void* stream);
+int64_t mp_knn_interpolate_f32(const float* x, int64_t ldx, int64_t n_x, int32_t C, int64_t n_y, int64_t k, void* ws,
+                               size_t ws_bytes, float* out, int64_t ldo, size_t out_bytes, void* stream);
+
 /* ---- other dtypes (csrc/mp_dtype.hip) -------------------------------------
  * torch_scatter 2.0.4 reduces any dtype ([U8/U9]); the fp32 hot path is
  * mp_aggregate_f32, these are the breadth path for the rest. */

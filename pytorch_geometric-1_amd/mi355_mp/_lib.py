@@ -204,6 +204,15 @@ SIGNATURES = {
     "mp_radius_fill": (i64, [i64, i64, i64, c_p, c_p, sz, c_p, sz, c_p]),
     "mp_point_edge_features_f32": (i64, [c_p, i64, i32, c_p, i64, i64, c_p, i64, i64, i32, c_p, c_p, i64, c_p,
                                                   i64, sz, c_p]),
+    # nearest neighbours (csrc/mp_knn.hip): int64 returns like the point-set calls, the sign tested by
+    # ops._count_call; the first three answer a question (mp_knn_path: 0 or 1, or -MP_ERR_ARG)
+    "mp_knn_max_k": (i64, []),
+    "mp_knn_max_d": (i64, []),
+    "mp_knn_path": (i64, [i32]),
+    "mp_knn_workspace": (sz, [i64, i64]),
+    "mp_knn_search_f32": (i64, [c_p, i64, i64, c_p, i64, i64, i32, c_p, c_p, i64, i64, c_p, sz, c_p, sz, c_p]),
+    "mp_knn_fill": (i64, [i64, i64, i64, c_p, c_p, sz, c_p, sz, c_p, sz, c_p]),
+    "mp_knn_interpolate_f32": (i64, [c_p, i64, i64, i32, i64, i64, c_p, sz, c_p, i64, sz, c_p]),
     # NNConv (csrc/mp_nnconv.hip): int64 returns like the two groups above, the sign tested by ops._count_call
     "mp_nnconv_ok": (i64, [i32, i32, i32]),        # an answer (0 or 1), not a status
     "mp_nnconv_edge_grad_width": (i64, [i32, i32]),  # an answer (0, 32 or 64), or -MP_ERR_ARG

@@ -3136,6 +3136,197 @@ def point_edge_features(x_src, pos_src, pos_dst, src, dst):
 
 
 # ---------------------------------------------------------------------------
+# Nearest neighbours (PyG 1.4.3 nn.knn / nn.knn_graph / nn.nearest /
+# nn.unpool.knn_interpolate [U]; csrc/mp_knn.hip)
+# ---------------------------------------------------------------------------
+
+KNN_MAX_K = 64          # one slot of the selection per lane (mp_knn_max_k)
+
+
+def knn_max_d():
+    """MP_KNN_MAX_D of the loaded library: the widest row knn searches (needs no GPU)."""
+    return int(_lib.native().mp_knn_max_d())
+
+
+def knn_path(D):
+    """0 = query and candidates in registers (D <= 8), 1 = the general-width
+    path: how mp_knn_search_f32 computes distances of width D (mp_knn_path;
+    needs no GPU).  ValueError for a D outside [1, MP_KNN_MAX_D]."""
+    p = int(_lib.native().mp_knn_path(int(D)))
+    if p < 0:
+        raise ValueError("knn: rows take 1 to %d columns (got %d)" % (knn_max_d(), int(D)))
+    return p
+
+
+def _knn_rows(pos, what):
+    """[n, D] float32 rows of a point or feature tensor (1 <= D <= MP_KNN_MAX_D; a
+    row stride is kept)."""
+    if pos.dtype != torch.float32:
+        raise TypeError("mi355_mp: %s must be float32 (got %s)" % (what, pos.dtype))
+    pos = pos.view(-1, 1) if pos.dim() == 1 else pos
+    if pos.dim() != 2:
+        raise ValueError("mi355_mp: %s must be [N] or [N, D]" % what)
+    if not 1 <= pos.shape[1] <= knn_max_d():
+        raise ValueError("knn: %s takes 1 to %d columns (got %d)" % (what, knn_max_d(), pos.shape[1]))
+    if pos.stride(1) != 1 or pos.stride(0) < pos.shape[1]:
+        pos = pos.contiguous()
+    return pos
+
+
+_one_graph = {}
+
+
+def _knn_layout(batch, n, device, what):
+    """_sorted_layout; the layout of batch None (one graph of n rows) is kept per
+    (device, n), so a repeated call copies nothing to the device."""
+    if batch is not None:
+        return _sorted_layout(batch, n, device, what)
+    key = (str(device), int(n))
+    layout = _one_graph.get(key)
+    if layout is None:
+        if len(_one_graph) >= 64:
+            _one_graph.clear()
+        layout = _one_graph[key] = batch_layout(None, n, device)
+    return layout
+
+
+class KnnSlab(object):
+    """What the search leaves on the device: the workspace of mp_knn_search_f32
+    (per query k neighbours, their d2 and a count, in ascending key; the scanned
+    counts), counts (int64 [4], counts[0] = E), and n_edges when the host knows E
+    without reading it (both batch vectors None), else None."""
+    __slots__ = ("ws", "ws_bytes", "counts", "n_x", "n_y", "k", "n_edges", "device")
+
+    def __init__(self, ws, ws_bytes, counts, n_x, n_y, k, n_edges, device):
+        self.ws, self.ws_bytes, self.counts, self.n_x, self.n_y = ws, ws_bytes, counts, n_x, n_y
+        self.k, self.n_edges, self.device = k, n_edges, device
+
+
+def knn_slab(x, y, k, batch_x=None, batch_y=None, what="knn"):
+    """mp_knn_search_f32: the k nearest rows of x for every row of y, left in a
+    KnnSlab.  No device-to-host read beyond the cached batch layouts."""
+    _lib.require_device(x, y, batch_x, batch_y)
+    k = int(k)
+    if k < 1:
+        raise ValueError("%s: k must be at least 1 (got %d)" % (what, k))
+    if k > KNN_MAX_K:
+        raise ValueError("%s: k = %d is above the limit of %d neighbours (MP_KNN_MAX_K)" % (what, k, KNN_MAX_K))
+    if (batch_x is None) != (batch_y is None):
+        raise ValueError("%s: batch_x and batch_y come together or not at all" % what)
+    x = _knn_rows(x.detach(), "x")
+    y = _knn_rows(y.detach(), "y")
+    if x.shape[1] != y.shape[1]:
+        raise ValueError("%s: x has %d columns, y %d" % (what, x.shape[1], y.shape[1]))
+    nat = _lib.native()
+    (n_x, D), n_y = x.shape, y.shape[0]
+    dev = x.device
+    lx = _knn_layout(batch_x, n_x, dev, "batch_x")
+    _knn_layout(batch_y, n_y, dev, "batch_y")
+    k = min(k, max(lx.max_n, 1))                  # a query never finds more than its graph holds
+    if n_y and k >= (1 << 31) // n_y:
+        raise ValueError("%s: n_y * k = %d * %d is not below 2^31" % (what, n_y, k))
+    if batch_y is not None:
+        batch_y = batch_y.contiguous()
+    counts = torch.empty(4, dtype=torch.int64, device=dev)
+    wsb = nat.mp_knn_workspace(n_y, k)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    _count_call(nat, "mp_knn_search_f32", _lib.ptr(x if n_x else None), x.stride(0), n_x,
+                _lib.ptr(y if n_y else None), y.stride(0), n_y, D, _lib.ptr(batch_y), lx.starts.data_ptr(),
+                lx.n_graphs, k, counts.data_ptr(), _lib.nbytes(counts), ws.data_ptr(), wsb, _lib.stream_ptr(dev))
+    n_edges = n_y * min(k, n_x) if batch_y is None else None
+    return KnnSlab(ws, wsb, counts, n_x, n_y, k, n_edges, dev)
+
+
+def knn_pairs(slab, weights=False):
+    """mp_knn_fill: the slab compacted to int64 [2, E] (row 0 indexes y, row 1 x;
+    sorted by y, within a y ascending in (d2, index)), and with `weights` the
+    normalised interpolation weight w_t / W_j of every pair, float32 [E].  One
+    device-to-host read (E) unless the slab knows it."""
+    nat = _lib.native()
+    E = slab.n_edges
+    if E is None:
+        E = slab.n_edges = int(slab.counts[0].item())
+    dev = slab.device
+    out = torch.empty((2, E), dtype=torch.int64, device=dev)
+    w = torch.empty(E, dtype=torch.float32, device=dev) if weights else None
+    _count_call(nat, "mp_knn_fill", slab.n_y, slab.k, E, _lib.ptr(out[0] if E else None),
+                _lib.ptr(out[1] if E else None), E * 8, _lib.ptr(w if E else None), _lib.nbytes(w), slab.ws.data_ptr(),
+                slab.ws_bytes, _lib.stream_ptr(dev))
+    return (out, w) if weights else out
+
+
+def knn_search(x, y, k, batch_x=None, batch_y=None):
+    """The k-nearest-neighbour search (mp_knn_search_f32 + mp_knn_fill): int64
+    [2, E], row 0 indices into y, row 1 into x; for every row of y the
+    min(k, n_g) rows of x of the same graph smallest under (d2(x_i, y_j), i) --
+    equal distances go to the lower index -- sorted by y and ascending in that
+    key within a y.
+
+    x [n_x, D], y [n_y, D] float32, 1 <= D <= MP_KNN_MAX_D (a row stride is kept);
+    batch_x / batch_y: sorted int64 or both None; 1 <= k <= 64.  ValueError for an
+    unsorted batch, a batch on one side only, k outside [1, 64], other widths.
+    At most one device-to-host read (E), beyond the cached batch layouts; none
+    when both batch vectors are None (then E = n_y * min(k, n_x))."""
+    return knn_pairs(knn_slab(x, y, k, batch_x, batch_y))
+
+
+class _KnnInterpolate(torch.autograd.Function):
+    """out[j] = (sum_t w_t x[i_t]) / (sum_t w_t) straight from the slab
+    (mp_knn_interpolate_f32): the forward never needs E.  Backward:
+    d x[i] = sum_{(j, i)} (w_ji / W_j) g[j], the engine's deterministic weighted
+    sum over a CSR of the compacted pairs keyed by the x index (one read of E, and
+    the CSR's own)."""
+
+    @staticmethod
+    def forward(ctx, x, slab):
+        nat = _lib.native()
+        n_x, C = x.shape
+        dev = x.device
+        out = torch.empty((slab.n_y, C), dtype=torch.float32, device=dev)
+        _count_call(nat, "mp_knn_interpolate_f32", _lib.ptr(x if n_x else None), x.stride(0), n_x, C, slab.n_y, slab.k,
+                    slab.ws.data_ptr(), slab.ws_bytes, _lib.ptr(out if slab.n_y else None), C, _lib.nbytes(out),
+                    _lib.stream_ptr(dev))
+        ctx.slab, ctx.shape = slab, (n_x, C)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        from .graph import CSR
+        slab = ctx.slab
+        n_x, C = ctx.shape
+        pairs, w = knn_pairs(slab, weights=True)
+        if pairs.shape[1] == 0:
+            return torch.zeros((n_x, C), dtype=torch.float32, device=g.device), None
+        g = _f32_2d(g, "grad")
+        by_x = CSR(pairs[1], pairs[0], n_x, slab.n_y)
+        gx, _ = _aggregate(by_x, "other", g, by_x.to_csr_order(w), "sum", 0, None)
+        return gx, None
+
+
+def knn_interpolate(x, pos_x, pos_y, batch_x=None, batch_y=None, k=3):
+    """Inverse-squared-distance interpolation of x [n_x, C] from pos_x onto pos_y
+    (upstream's nn.unpool.knn_interpolate): float32 [n_y, C],
+    out[j] = (sum_t w_t x[i_t]) / (sum_t w_t) over the k nearest i_t of pos_y[j] in
+    knn order, w_t = 1 / max(d2_t, 1e-16), both sums in fp32 in the order
+    t = 0 .. c - 1.  A y whose graph holds no x gets zeros.  Differentiable in x
+    only (upstream computes the weights under no_grad).  The forward makes no
+    device-to-host read beyond the cached batch layouts."""
+    _lib.require_device(x, pos_x, pos_y, batch_x, batch_y)
+    x = _f32_2d(x, "x")
+    if x.shape[1] < 1:
+        raise ValueError("knn_interpolate: x must have at least one column")
+    if x.stride(0) < x.shape[1]:
+        x = x.contiguous()
+    n_x = pos_x.shape[0]
+    if x.shape[0] != n_x:
+        raise ValueError("knn_interpolate: x has %d rows, pos_x %d" % (x.shape[0], n_x))
+    slab = knn_slab(pos_x, pos_y, k, batch_x, batch_y, what="knn_interpolate")
+    return _KnnInterpolate.apply(x, slab)
+
+
+# ---------------------------------------------------------------------------
 # Attention readout (PyG 1.4.3 nn.glob.Set2Set / GlobalAttention [U]; csrc/mp_glob.hip)
 # ---------------------------------------------------------------------------
 

@@ -12,6 +12,7 @@ from .point_conv import PointConv
 from .nn_conv import NNConv
 from .rgcn_conv import RGCNConv
 from .dna_conv import DNAConv
+from .edge_conv import EdgeConv, DynamicEdgeConv
 
 __all__ = ["MessagePassing", "GCNConv", "GATConv", "SAGEConv", "GraphConv", "ChebConv", "AGNNConv", "SGConv", "GINConv",
-           "SplineConv", "PointConv", "NNConv", "RGCNConv", "DNAConv"]
+           "SplineConv", "PointConv", "NNConv", "RGCNConv", "DNAConv", "EdgeConv", "DynamicEdgeConv"]
