@@ -18,6 +18,7 @@
 #include <float.h>
 
 #include "mp_agg.h"
+#include "mp_flat_ring.h"
 
 // Kernel-shape constants of the plain aggregation (chosen like mp_agg.h's).
 namespace mp {
@@ -37,7 +38,8 @@ struct SumRed : RedFlags {
   };
   float acc[VEC];
   // the bias features of this lane, read once per task (preload_bias) by the
-  // short-row passes of mp_aggregate_tiles_f32 (k_agg_flat XM != 0)
+  // short-row passes of mp_aggregate_tiles_f32 (k_agg_flat XM != 0) and by the
+  // rolling gather window of k_agg_flat's scalar-batch loop
   float bv[VEC];
   bool pre = false;
   int h = 0;  // unused (GAT only)
@@ -49,8 +51,12 @@ struct SumRed : RedFlags {
   // retires in order) also drains every gather issued before it -- the next
   // rows' prefetched batch.  On the sharded step's short rows (4.4 edges a row)
   // that cost the interior pass 19 % (tools/exp_interior.py: 0.287 -> 0.245
-  // ms); on the one-GPU kernel's long rows the per-row load measured faster
-  // (1-3 %), so only the tile launches take it once per task.
+  // ms), so the tile launches take it once per task.  On the one-GPU kernel's
+  // long rows the per-row load measured 1-3 % faster while the loop drained its
+  // gathers at every batch's end anyway; under the rolling gather window it is
+  // the slower form (config 2, ring of 4: 6.79 ms against 6.45 ms with the bias
+  // per task), so the window's instances take it once per task too.  Whole-batch
+  // instances outside the tile launches keep the load per row.
   __device__ __forceinline__ void preload_bias(const AggArgs& p, int f, bool act) {
     if (p.bias && act) {
       Frag<VEC> b = load_frag<VEC>(p.bias + f);
@@ -69,18 +75,38 @@ struct SumRed : RedFlags {
     return load_frag<VEC>(p.bias + f);
   }
 
-  __device__ __forceinline__ void begin(const AggArgs& p, int64_t row, bool owned, int f, bool act) {
+  // SETTLE: wait for the row's initial value where it is loaded.  Left pending,
+  // the load is one that every later accumulate may have to wait for, on every
+  // path that reaches it: the compiler then puts s_waitcnt vmcnt(0) in front of
+  // each accumulate of k_agg_flat's scalar-batch loop, and the wave sits until
+  // all its gathers have landed before it consumes the first.
+  template <bool SETTLE>
+  __device__ __forceinline__ void begin_at(const AggArgs& p, int64_t row, bool owned, int f, bool act) {
 #pragma unroll
     for (int k = 0; k < VEC; ++k) acc[k] = 0.f;
     if (owned && (p.flags & MP_FLAG_INIT_FROM_OUT) && act) {
       Frag<VEC> o = load_frag<VEC>(p.out + row * p.ldo + f);
 #pragma unroll
-      for (int k = 0; k < VEC; ++k) acc[k] = o.v[k];
+      for (int k = 0; k < VEC; ++k) {
+        if constexpr (SETTLE) asm volatile("" : "+v"(o.v[k]));
+        acc[k] = o.v[k];
+      }
     }
+  }
+  __device__ __forceinline__ void begin(const AggArgs& p, int64_t row, bool owned, int f, bool act) {
+    begin_at<false>(p, row, owned, f, act);
   }
   __device__ __forceinline__ void consume(const Frag<VEC>& v, float wt, int, float) {
 #pragma unroll
     for (int k = 0; k < VEC; ++k) acc[k] = __fadd_rn(acc[k], HAS_W ? __fmul_rn(wt, v.v[k]) : v.v[k]);
+  }
+  // The accumulate so far stays in front of what follows.  k_agg_flat's rolling
+  // window refills a ring entry right behind the accumulate that consumed it;
+  // with the accumulate moved below the refill, the refill lands in another
+  // register and is copied into the entry behind an s_waitcnt vmcnt(0).
+  __device__ __forceinline__ void pin() {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) asm volatile("" : "+v"(acc[k]) : : "memory");
   }
   __device__ __forceinline__ void save(PRef r, bool) const {
     Frag<VEC> o;
@@ -555,7 +581,7 @@ __device__ __forceinline__ void scalar_batch(const T* a, int64_t n, int64_t e, T
     for (int u = 0; u < U; ++u) v[u] = t[u];
   } else {
 #pragma unroll
-    for (int u = 0; u < U; ++u) v[u] = ((ct*)a)[e + u < n ? e + u : n - 1];
+    for (int u = 0; u < U; ++u) v[u] = ((ct*)a)[batch_slot(e, u, n)];
   }
 }
 
@@ -571,6 +597,28 @@ __device__ __forceinline__ void scalar_batch(const T* a, int64_t n, int64_t e, T
 // tile-major operands.  Compile-time, one feature per instance, so every other
 // launch runs the kernel without their per-block and per-row work (measured:
 // both features as run-time branches of one instance cost short-row passes 13 %).
+// Ring depth of the scalar-batch loop's rolling gather window, per family of
+// launches; 0: batches of U issued and consumed whole, the loop as it was
+// before the window.  U stays the instance's name.  Measured (main kernel,
+// bitwise-equal outputs; DESIGN Appendix A):
+//  * x beyond the Infinity Cache, plain operands (config 2 / config 5): a ring
+//    of 4 runs 6.33 / 14.06 ms against 6.57 / 14.65 ms for batches of 8.  With
+//    the ring still draining at every row's end, rings of 2, 3, 4, 5, 6 and 8
+//    ran 8.21, 7.21, 6.45, 6.55, 6.77 and 6.97 ms on config 2;
+//  * the sharded step's far tile launches without per-row options run this
+//    same instance: interior 0.238 -> 0.202 ms, send packing 0.643 -> 0.614,
+//    boundary pull unchanged (tools/exp_interior.py);
+//  * the XM != 0 and tile-major instances keep whole batches: rings of 4 and 8
+//    lost 2 - 5 % on some pass each when measured with the row-end drain
+//    still in; not measured again without it;
+//  * x inside the Infinity Cache (U = 16): a ring of 16 ran 2.76 ms against
+//    3.03 ms at Reddit scale (with the drain); not switched on, the tile
+//    launches that share the instance are not measured.
+template <int VEC, int U, int XM, bool TM>
+constexpr int flat_ring() {
+  return (VEC == 1 && U == kU_Vec1Far && XM == 0 && !TM) ? 4 : 0;
+}
+
 template <class Red, int VEC, int U, int L, bool GA = false, bool SM = false, int XM = 0, bool TM = false>
 __global__ __launch_bounds__(kBlock) void k_agg_flat(AggArgs p) {
   static_assert(!Red::kGat && !Red::kGatB && !Red::kHW, "flat loop: sum/mean/max/min reducers");
@@ -578,6 +626,9 @@ __global__ __launch_bounds__(kBlock) void k_agg_flat(AggArgs p) {
   static_assert(!SM || (L == 64 && !GA && !Red::kEid), "scalar batches: 64-lane sum/mean tasks");
   static_assert(!(XM || TM) || (SM && VEC == 1), "tile-major / skipped rows: the scalar-batch kernel, 64-feature tiles");
   constexpr bool kSkip = XM == 2, kFlags = XM == 1;
+  constexpr int R = SM ? flat_ring<VEC, U, XM, TM>() : 0;  // rolling gather window of R entries
+  constexpr bool kRoll = R > 0;
+  constexpr int B = kRoll ? R : U;                     // slots per scalar batch
   using GR = Grp<L>;
   const int lane = lane_id();
   const int gl = lane & (L - 1);
@@ -612,12 +663,18 @@ __global__ __launch_bounds__(kBlock) void k_agg_flat(AggArgs p) {
   const int64_t e_end = GR::un(p.wave_slot[w + 1]);
 
   Red red(p, f, act);
-  if constexpr (XM != 0) red.preload_bias(p, f, act);  // the tile launches: sum / mean only
+  // the tile launches, and the rolling window (sum / mean only): a bias load per
+  // row would drain the gather ring at every row's end (config 2, ring of 4:
+  // 6.79 ms with the load per row, 6.45 ms with it per task)
+  if constexpr (XM != 0 || kRoll) red.preload_bias(p, f, act);
+  // a row's accumulator starts (the rolling window: with its initial value landed)
+  auto begin_row = [&](int64_t rr, bool owned) {
+    if constexpr (kRoll) red.template begin_at<true>(p, rr, owned, f, act);
+    else red.begin(p, rr, owned, f, act);
+  };
   // an owned row opens (rs_ / re_: its slot range); an empty one is skipped
   // (no load of out) under MP_FLAG_SKIP_EMPTY
-  auto open_row = [&](int rr, int64_t rs_, int64_t re_) {
-    red.begin(p, rr, !(kSkip && re_ == rs_), f, act);
-  };
+  auto open_row = [&](int rr, int64_t rs_, int64_t re_) { begin_row(rr, !(kSkip && re_ == rs_)); };
 
   std::conditional_t<GA, GatAlphaWin, SlotWin<Red::kW, Red::kEid, L>> win;
   if constexpr (GA) {
@@ -626,10 +683,10 @@ __global__ __launch_bounds__(kBlock) void k_agg_flat(AggArgs p) {
   } else if constexpr (!SM) {
     win.init(p, e_begin, e_end, gl);
   }
-  [[maybe_unused]] int c_nxt[U];
+  [[maybe_unused]] int c_nxt[B];
   if constexpr (SM) {
     xr = __builtin_amdgcn_make_buffer_rsrc((void*)x_tile, (short)0, (int)p.x_bytes, 0x00020000);
-    if (e_begin < e_end) scalar_batch<U>(p.col, p.n_edges, e_begin, c_nxt);
+    if (e_begin < e_end) scalar_batch<B>(p.col, p.n_edges, e_begin, c_nxt);
   }
   // row window: rowptr (and, kFlags, the per-row bias flags) of rows [rbase,
   // rbase + L) across the lanes.  A kFlags refill for row pointer r starts at
@@ -644,6 +701,10 @@ __global__ __launch_bounds__(kBlock) void k_agg_flat(AggArgs p) {
       rbase = kFlags ? r - 1 : r;
       rp = (rbase + gl <= p.n_rows) ? p.rowptr[rbase + gl] : 0;
       if constexpr (kFlags) bw = (rbase + gl < p.n_rows) ? p.bias_rows[rbase + gl] : 1;
+      // the rolling window: the refill is waited for here, once per 64 rows.  Left
+      // pending, it puts an s_waitcnt vmcnt(0) in front of the v_readlane below on
+      // every path, and the ring drains at every row's end.
+      if constexpr (kRoll) asm volatile("" : "+v"(rp));
     }
     return GR::bc(rp, r - rbase);
   };
@@ -664,7 +725,7 @@ __global__ __launch_bounds__(kBlock) void k_agg_flat(AggArgs p) {
   int r = r_first;
   int64_t rs = ce, re = ce;
   if (cont) {
-    red.begin(p, r_first - 1, false, f, act);
+    begin_row(r_first - 1, false);
   } else if (r < r_last) {
     re = row_ptr(r + 1);
     open_row(r, rs, re);
@@ -689,7 +750,58 @@ __global__ __launch_bounds__(kBlock) void k_agg_flat(AggArgs p) {
     }
   };
 
-  for (int64_t e = e_begin; e < e_end;) {
+  if constexpr (kRoll) {
+    // Rolling gather window (mp_flat_ring.h): a ring of R gathers.  Every batch
+    // but the task's last refills entry u with slot e + R + u as soon as slot
+    // e + u is consumed, so the wave keeps R - 1 .. R gathers in flight until
+    // the task's last batch instead of draining to none at the end of every
+    // batch.  Batches start at e_begin + k*R.  The refills of batch k read the
+    // columns of batch k + 1 (c_nxt); once the last of them is issued, the
+    // columns of batch k + 2 and the weights of batch k + 1 are loaded into the
+    // same SGPRs, and land while batch k + 1 waits for its first row, R - 1
+    // gathers behind it.  (A second SGPR set for each, loaded a batch earlier,
+    // took the kernel from 88 to 106 SGPRs: one resident block per CU fewer.)
+    // The refills are unconditional: a refill under a per-slot condition is
+    // loaded into a temporary and copied behind an s_waitcnt vmcnt(0).  Those
+    // of the last-but-one batch that fall past e_end are never consumed, like
+    // the tail of the last batch's loads before.  Slots are consumed in the
+    // same order as ever.
+    Frag<VEC> v[R];
+    [[maybe_unused]] float w_cur[R];
+    int64_t e = e_begin;
+    if (e < e_end) {
+#pragma unroll
+      for (int u = 0; u < R; ++u) v[u] = load_frag_buf<VEC>(xr, foff, (uint32_t)c_nxt[u] * (uint32_t)ldxb);
+      if (ring_refills(e, e_end, R)) scalar_batch<R>(p.col, p.n_edges, e + R, c_nxt);
+      if constexpr (Red::kW) scalar_batch<R>(p.w, p.n_edges, e, w_cur);
+    }
+    for (; ring_refills(e, e_end, R); e += R) {
+#pragma unroll
+      for (int u = 0; u < R; ++u) {
+        advance(e + u);
+        float wt = 1.f;
+        if constexpr (Red::kW) wt = w_cur[u];
+        red.consume(v[u], wt, 0, 0.f);
+        red.pin();
+        v[u] = load_frag_buf<VEC>(xr, foff, (uint32_t)c_nxt[u] * (uint32_t)ldxb);
+      }
+      if (ring_loads_cols(e, e_end, R)) scalar_batch<R>(p.col, p.n_edges, e + 2 * R, c_nxt);
+      if constexpr (Red::kW) scalar_batch<R>(p.w, p.n_edges, e + R, w_cur);
+    }
+    if (e < e_end) {
+      const int n = ring_last(e, e_end);
+#pragma unroll
+      for (int u = 0; u < R; ++u) {
+        if (u < n) {
+          advance(e + u);
+          float wt = 1.f;
+          if constexpr (Red::kW) wt = w_cur[u];
+          red.consume(v[u], wt, 0, 0.f);
+        }
+      }
+    }
+  }
+  if constexpr (!kRoll) for (int64_t e = e_begin; e < e_end;) {
     if constexpr (SM) {
       // batches start at e_begin + k*U: every batch but the task's last is full
       const int64_t rem = e_end - e;
