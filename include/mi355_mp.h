@@ -1332,6 +1332,83 @@ int64_t mp_knn_fill(int64_t n_y, int64_t k, int64_t n_edges, int64_t* out_y, int
 int64_t mp_knn_interpolate_f32(const float* x, int64_t ldx, int64_t n_x, int32_t C, int64_t n_y, int64_t k, void* ws,
                                size_t ws_bytes, float* out, int64_t ldo, size_t out_bytes, void* stream);
 
+/* ---- The dense family: DiffPool, DenseSAGEConv, to_dense_* (csrc/mp_dense.hip)
+ * PyG 1.4.3's nn.dense.dense_diff_pool [U], per graph b of a dense batch, with
+ * x [B, N, F], adj [B, N, N], s [B, N, C] and mask [B, N] (bytes, 0 = padding;
+ * NULL = every row live), all contiguous fp32:
+ *   P = softmax(s, -1) * mask          T = adj P            V = adj^T P
+ *   out [B, C, F] = P^T (x * mask)     out_adj [B, C, C] = P^T T
+ *   q_b = sum_ij (adj_ij - p_i . p_j)^2  over all N x N entries, padding included
+ *   h_b = sum_ic -p_ic log(p_ic + 1e-15)
+ *   loss [4] = (link, ent, Q, H):  Q = sum_b q_b, H = sum_b h_b,
+ *              link = sqrt(Q) / (B N N), ent = H / (B N)
+ * The residual is formed entry by entry (never as |adj|^2 - 2 tr + |P^T P|^2) and
+ * nothing of size [B, N, N] is allocated.  P, T and V ([B, N, C] each) are
+ * written for the backward, which never reads adj: with gOut [B, C, F], gOA
+ * [B, C, C] and g_loss [2] = (gl, ge) on the device (each may be NULL = zero),
+ *   k  = gl / (sqrt(Q) B N N), 0 when Q is 0
+ *   dP = x gOut^T + T gOA^T + V gOA - k (T + V - 2 P (P^T P))
+ *        - (ge / (B N)) (log(P + 1e-15) + P / (P + 1e-15))
+ *   ds = P * (dP - rowsum(dP * P))      (the softmax backward of mask * dP)
+ *   dx = P gOut                          (P's masked rows are zero; dx may be NULL)
+ * adj receives no gradient from these calls.
+ * Forms, from mp_diff_pool_path(N, C, F) (needs no GPU; non-decreasing in N):
+ *   0  one workgroup per graph, P, T and V in LDS, adj staged once in row chunks
+ *   1  row tiles of a batched fp32 GEMM core; the residual's tile partials and
+ *      the rows' entropies go to the workspace and are added in a fixed order
+ * No float atomics; every sum has a fixed order, so a call's results are the
+ * same bits run to run.  Any B, N, C, F >= 1 within B <= 65535, N <= 2^22 and
+ * fewer than 2^24 tiles of 64 x 64 per launch (B * ceil(N / 64)^2 and B * ceil(N /
+ * 64) * ceil(max(C, F) / 64)); beyond that, or with a NULL or misaligned (float:
+ * 4 bytes, ws: 16) pointer or an array shorter than the call writes, the call is
+ * refused before any launch.
+ * ws: mp_diff_pool_workspace / mp_diff_pool_bwd_workspace(B, N, C, F) bytes
+ * (csrc/mp_dense.hip DiffPoolWs, DiffPoolBwdWs), required.
+ *
+ * mp_dense_mean_agg_f32, DenseSAGEConv's aggregation: with A^ = adj, its diagonal
+ * read as 1 when add_loop (adj itself is never copied or written),
+ *   transpose = 0:  deg_out[b, i] = sum_j A^_ij,  out[b, i, :] = (sum_j A^_ij x[b, j, :]) / max(deg, 1)
+ *   transpose = 1:  out[b, j, :] = sum_i A^_ij x[b, i, :] / max(deg_in[b, i], 1)
+ * one pass over adj each; the second is the first's gradient for x (x = the
+ * incoming gradient, deg_in = the saved deg_out).
+ *
+ * mp_to_dense_batch_f32: over the segment starts of a sorted batch vector
+ * (starts [B + 1], as the readout above), out[g, i, :] = x[starts[g] + i, :] for
+ * i < n_g, else fill; mask[g, i] = i < n_g (bytes).  Nmax must be at least the
+ * largest graph.  mp_to_dense_batch_bwd_f32 is the row gather dx[starts[g] + i,
+ * :] = g[g, i, :].  mp_to_dense_adj_f32: out [B, Nmax, Nmax] (D = 0, edge_attr
+ * NULL) or [B, Nmax, Nmax, D] is zeroed, then edge e = (row, col) of graph g =
+ * batch[row] (batch NULL: one graph) sets cell (g, row - starts[g], col -
+ * starts[g]) to 1, or to edge_attr[e, :]; of several edges of one cell the last
+ * in edge order wins (an integer maximum over edge indices in the workspace,
+ * mp_to_dense_adj_workspace(B, Nmax, D) bytes).  An edge whose ends do not lie
+ * in one graph's [0, Nmax) is skipped.
+ * Every call returns the launches enqueued, >= 0, or -(MP_ERR_* code). */
+int64_t mp_diff_pool_path(int64_t N, int32_t C, int32_t F);
+size_t mp_diff_pool_workspace(int64_t B, int64_t N, int32_t C, int32_t F);
+size_t mp_diff_pool_bwd_workspace(int64_t B, int64_t N, int32_t C, int32_t F);
+int64_t mp_dense_diff_pool_f32(const float* x, const float* adj, const float* s, const uint8_t* mask, int64_t B,
+                               int64_t N, int32_t C, int32_t F, float* out, size_t out_bytes, float* out_adj,
+                               size_t out_adj_bytes, float* loss, size_t loss_bytes, float* P, size_t P_bytes,
+                               float* T, size_t T_bytes, float* V, size_t V_bytes, void* ws, size_t ws_bytes,
+                               void* stream);
+int64_t mp_dense_diff_pool_bwd_f32(const float* g_out, const float* g_oa, const float* g_loss, const float* x,
+                                   const float* P, const float* T, const float* V, const float* loss, int64_t B,
+                                   int64_t N, int32_t C, int32_t F, float* dx, size_t dx_bytes, float* ds,
+                                   size_t ds_bytes, void* ws, size_t ws_bytes, void* stream);
+int64_t mp_dense_mean_agg_f32(const float* adj, const float* x, int64_t B, int64_t N, int32_t F, int32_t add_loop,
+                              int32_t transpose, const float* deg_in, float* out, size_t out_bytes, float* deg_out,
+                              size_t deg_out_bytes, void* stream);
+int64_t mp_to_dense_batch_f32(const float* x, int64_t n, int32_t F, const int64_t* starts, int64_t B, int64_t Nmax,
+                              float fill, float* out, size_t out_bytes, uint8_t* mask, size_t mask_bytes,
+                              void* stream);
+int64_t mp_to_dense_batch_bwd_f32(const float* g, int64_t n, int32_t F, const int64_t* starts, int64_t B,
+                                  int64_t Nmax, float* dx, size_t dx_bytes, void* stream);
+size_t mp_to_dense_adj_workspace(int64_t B, int64_t Nmax, int32_t D);
+int64_t mp_to_dense_adj_f32(const int64_t* row, const int64_t* col, int64_t E, const float* edge_attr, int32_t D,
+                            const int64_t* batch, int64_t n, const int64_t* starts, int64_t B, int64_t Nmax,
+                            float* out, size_t out_bytes, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- other dtypes (csrc/mp_dtype.hip) -------------------------------------
  * torch_scatter 2.0.4 reduces any dtype ([U8/U9]); the fp32 hot path is
  * mp_aggregate_f32, these are the breadth path for the rest. */

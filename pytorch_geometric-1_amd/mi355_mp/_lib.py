@@ -252,6 +252,19 @@ SIGNATURES = {
                                       i64, sz, c_p, sz, i32, i32, i32, u64, f32, c_p, i64, sz, c_p, i64, sz, c_p, sz,
                                       c_p]),
     "mp_dna_dropout_keep": (i64, [u64, f32, i32, i32, i64, c_p, sz, c_p]),
+    # the dense family (csrc/mp_dense.hip): int64 returns again, the sign tested by ops._count_call
+    "mp_diff_pool_path": (i64, [i64, i32, i32]),   # an answer (0 or 1), or -MP_ERR_ARG
+    "mp_diff_pool_workspace": (sz, [i64, i64, i32, i32]),
+    "mp_diff_pool_bwd_workspace": (sz, [i64, i64, i32, i32]),
+    "mp_dense_diff_pool_f32": (i64, [c_p, c_p, c_p, c_p, i64, i64, i32, i32, c_p, sz, c_p, sz, c_p, sz, c_p, sz, c_p,
+                                     sz, c_p, sz, c_p, sz, c_p]),
+    "mp_dense_diff_pool_bwd_f32": (i64, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, i64, i64, i32, i32, c_p, sz, c_p, sz,
+                                         c_p, sz, c_p]),
+    "mp_dense_mean_agg_f32": (i64, [c_p, c_p, i64, i64, i32, i32, i32, c_p, c_p, sz, c_p, sz, c_p]),
+    "mp_to_dense_batch_f32": (i64, [c_p, i64, i32, c_p, i64, i64, f32, c_p, sz, c_p, sz, c_p]),
+    "mp_to_dense_batch_bwd_f32": (i64, [c_p, i64, i32, c_p, i64, i64, c_p, sz, c_p]),
+    "mp_to_dense_adj_workspace": (sz, [i64, i64, i32]),
+    "mp_to_dense_adj_f32": (i64, [c_p, c_p, i64, c_p, i32, c_p, i64, c_p, i64, i64, c_p, sz, c_p, sz, c_p]),
 }
 
 # Of the symbols declared `int` / `int32_t`, these answer a question (a version,

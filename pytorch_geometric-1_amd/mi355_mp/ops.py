@@ -3468,3 +3468,232 @@ def attention_readout(x, layout, q=None, score=None, out=None, col=0):
         if out.requires_grad:
             raise ValueError("mi355_mp: out is overwritten in place and must not require a gradient")
     return _AttentionReadout.apply(x, q, score, layout, out, int(col))
+
+
+# ---------------------------------------------------------------------------
+# The dense family (PyG 1.4.3 nn.dense, utils.to_dense_batch / to_dense_adj [U]; csrc/mp_dense.hip)
+# ---------------------------------------------------------------------------
+
+def diff_pool_path(N, C, F):
+    """0 = one workgroup per graph (P, T and V in LDS), 1 = row tiles of the GEMM
+    core with partials in the workspace: how mp_dense_diff_pool_f32 runs graphs
+    of N nodes, C clusters and F features (mp_diff_pool_path; needs no GPU).
+    ValueError unless all three are >= 1."""
+    p = int(_lib.native().mp_diff_pool_path(int(N), int(C), int(F)))
+    if p < 0:
+        raise ValueError("diff_pool_path: N = %d, C = %d, F = %d (each >= 1)" % (N, C, F))
+    return p
+
+
+def _dense_3d(t, what, last=None):
+    if t.dtype != torch.float32 or t.dim() != 3 or (last is not None and t.shape[2] != last):
+        raise ValueError("mi355_mp: %s must be float32 [B, N, %s] (got %s %s)"
+                         % (what, "*" if last is None else last, t.dtype, tuple(t.shape)))
+    return t.contiguous()
+
+
+def _dense_mask(mask, B, N):
+    if mask is None:
+        return None
+    if mask.numel() != B * N:
+        raise ValueError("mi355_mp: mask must hold [%d, %d] entries (got %s)" % (B, N, tuple(mask.shape)))
+    return (mask.reshape(B, N) != 0).to(torch.uint8).contiguous()
+
+
+class _DenseDiffPool(torch.autograd.Function):
+    """(out, out_adj, link_loss, ent_loss) of mp_dense_diff_pool_f32; saves x and
+    the forward's P, T, V and loss sums, so the backward
+    (mp_dense_diff_pool_bwd_f32) never reads adj.  adj gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, x, adj, s, mask):
+        nat = _lib.native()
+        B, N, F = x.shape
+        C = s.shape[2]
+        dev = x.device
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)   # noqa: E731
+        out, out_adj, loss = new(B, C, F), new(B, C, C), new(4)
+        P, T, V = new(B, N, C), new(B, N, C), new(B, N, C)
+        wsb = nat.mp_diff_pool_workspace(B, N, C, F)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        _count_call(nat, "mp_dense_diff_pool_f32", x.data_ptr(), adj.data_ptr(), s.data_ptr(), _lib.ptr(mask), B, N, C,
+                    F, out.data_ptr(), _lib.nbytes(out), out_adj.data_ptr(), _lib.nbytes(out_adj), loss.data_ptr(),
+                    _lib.nbytes(loss), P.data_ptr(), _lib.nbytes(P), T.data_ptr(), _lib.nbytes(T), V.data_ptr(),
+                    _lib.nbytes(V), ws.data_ptr(), wsb, _lib.stream_ptr(dev))
+        ctx.save_for_backward(x, P, T, V, loss)
+        ctx.mark_non_differentiable(P)
+        return out, out_adj, loss[0], loss[1], P
+
+    @staticmethod
+    def backward(ctx, g_out, g_oa, g_link, g_ent, _g_p):
+        nat = _lib.native()
+        x, P, T, V, loss = ctx.saved_tensors
+        B, N, F = x.shape
+        C = P.shape[2]
+        dev = x.device
+        need_x, need_s = ctx.needs_input_grad[0], ctx.needs_input_grad[2]
+        if not need_x and not need_s:
+            return None, None, None, None
+        g_out = None if g_out is None else g_out.contiguous()
+        g_oa = None if g_oa is None else g_oa.contiguous()
+        g_loss = None
+        if g_link is not None or g_ent is not None:
+            zero = loss.new_zeros(())
+            g_loss = torch.stack([zero if g_link is None else g_link.reshape(()),
+                                  zero if g_ent is None else g_ent.reshape(())]).contiguous()
+        dx = torch.empty((B, N, F), dtype=torch.float32, device=dev) if need_x else None
+        ds = torch.empty((B, N, C), dtype=torch.float32, device=dev)
+        wsb = nat.mp_diff_pool_bwd_workspace(B, N, C, F)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+        _count_call(nat, "mp_dense_diff_pool_bwd_f32", _lib.ptr(g_out), _lib.ptr(g_oa), _lib.ptr(g_loss), x.data_ptr(),
+                    P.data_ptr(), T.data_ptr(), V.data_ptr(), loss.data_ptr(), B, N, C, F, _lib.ptr(dx),
+                    _lib.nbytes(dx), ds.data_ptr(), _lib.nbytes(ds), ws.data_ptr(), wsb, _lib.stream_ptr(dev))
+        return dx, None, ds if need_s else None, None
+
+
+def dense_diff_pool(x, adj, s, mask=None, want_assignment=False):
+    """The fused dense_diff_pool (include/mi355_mp.h "The dense family"): x [B, N,
+    F], adj [B, N, N], s [B, N, C] float32 on the GPU, mask [B, N] (any dtype,
+    non-zero = a node) or None.  Returns (out [B, C, F], out_adj [B, C, C],
+    link_loss, ent_loss), and P = softmax(s) * mask as a fifth value with
+    want_assignment.  Differentiable in x and s; adj must not require a gradient
+    (the fused backward never forms one)."""
+    _lib.require_device(x, adj, s, mask)
+    if adj.requires_grad:
+        raise ValueError("mi355_mp: the fused dense_diff_pool gives adj no gradient; adj.requires_grad is set")
+    x = _dense_3d(x, "x")
+    B, N, F = x.shape
+    adj = _dense_3d(adj, "adj", N)
+    s = _dense_3d(s, "s")
+    C = s.shape[2]
+    if adj.shape[:2] != (B, N) or s.shape[:2] != (B, N) or min(B, N, C, F) < 1:
+        raise ValueError("mi355_mp: dense_diff_pool takes x [B, N, F], adj [B, N, N], s [B, N, C], all >= 1 (got %s, "
+                         "%s, %s)" % (tuple(x.shape), tuple(adj.shape), tuple(s.shape)))
+    res = _DenseDiffPool.apply(x, adj, s, _dense_mask(mask, B, N))
+    return res if want_assignment else res[:4]
+
+
+class _DenseMeanAgg(torch.autograd.Function):
+    """mp_dense_mean_agg_f32 and, as its backward for x, the same call over the
+    transposed adjacency with the saved degrees."""
+
+    @staticmethod
+    def forward(ctx, x, adj, add_loop):
+        nat = _lib.native()
+        B, N, F = x.shape
+        dev = x.device
+        out = torch.empty((B, N, F), dtype=torch.float32, device=dev)
+        deg = torch.empty((B, N), dtype=torch.float32, device=dev)
+        _count_call(nat, "mp_dense_mean_agg_f32", adj.data_ptr(), x.data_ptr(), B, N, F, int(add_loop), 0, None,
+                    out.data_ptr(), _lib.nbytes(out), deg.data_ptr(), _lib.nbytes(deg), _lib.stream_ptr(dev))
+        ctx.add_loop = int(add_loop)
+        ctx.save_for_backward(adj, deg)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        nat = _lib.native()
+        adj, deg = ctx.saved_tensors
+        g = g.contiguous()
+        B, N, F = g.shape
+        dx = torch.empty_like(g)
+        _count_call(nat, "mp_dense_mean_agg_f32", adj.data_ptr(), g.data_ptr(), B, N, F, ctx.add_loop, 1,
+                    deg.data_ptr(), dx.data_ptr(), _lib.nbytes(dx), None, 0, _lib.stream_ptr(g.device))
+        return dx, None, None
+
+
+def dense_mean_agg(x, adj, add_loop=True):
+    """agg[b, i] = sum_j A^_ij x[b, j] / max(sum_j A^_ij, 1) with A^ = adj, its
+    diagonal read as 1 when add_loop (adj is not copied): x [B, N, F], adj [B, N,
+    N] float32 on the GPU.  Differentiable in x; adj must not require a gradient."""
+    _lib.require_device(x, adj)
+    if adj.requires_grad:
+        raise ValueError("mi355_mp: the fused dense_mean_agg gives adj no gradient; adj.requires_grad is set")
+    x = _dense_3d(x, "x")
+    B, N, F = x.shape
+    adj = _dense_3d(adj, "adj", N)
+    if adj.shape[:2] != (B, N) or min(B, N, F) < 1:
+        raise ValueError("mi355_mp: dense_mean_agg takes x [B, N, F] and adj [B, N, N], all >= 1 (got %s, %s)"
+                         % (tuple(x.shape), tuple(adj.shape)))
+    return _DenseMeanAgg.apply(x, adj, bool(add_loop))
+
+
+class _ToDenseBatch(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, layout, fill):
+        nat = _lib.native()
+        n, F = x.shape
+        B, Nmax = layout.n_graphs, layout.max_n
+        dev = x.device
+        out = torch.empty((B, Nmax, F), dtype=torch.float32, device=dev)
+        mask = torch.empty((B, Nmax), dtype=torch.uint8, device=dev)
+        _count_call(nat, "mp_to_dense_batch_f32", _lib.ptr(x if n else None), n, F, layout.starts.data_ptr(), B, Nmax,
+                    float(fill), _lib.ptr(out if out.numel() else None), _lib.nbytes(out),
+                    _lib.ptr(mask if mask.numel() else None), _lib.nbytes(mask), _lib.stream_ptr(dev))
+        ctx.layout, ctx.n = layout, n
+        mask = mask.bool()
+        ctx.mark_non_differentiable(mask)
+        return out, mask
+
+    @staticmethod
+    def backward(ctx, g, _g_mask):
+        nat = _lib.native()
+        layout, n = ctx.layout, ctx.n
+        g = g.contiguous()
+        F = g.shape[2]
+        dx = torch.empty((n, F), dtype=torch.float32, device=g.device)
+        _count_call(nat, "mp_to_dense_batch_bwd_f32", _lib.ptr(g if g.numel() else None), n, F,
+                    layout.starts.data_ptr(), layout.n_graphs, layout.max_n, _lib.ptr(dx if n else None),
+                    _lib.nbytes(dx), _lib.stream_ptr(g.device))
+        return dx, None, None
+
+
+def to_dense_batch(x, layout, fill_value=0.0):
+    """(dense [B, max_n, F], mask [B, max_n] bool) of the rows x [n, F] (float32, on
+    the GPU) under the BatchLayout of a sorted batch vector (mp_to_dense_batch_f32);
+    padding rows hold fill_value.  Differentiable in x (a row gather)."""
+    _lib.require_device(x, layout.starts)
+    if layout.unsorted:
+        raise ValueError("mi355_mp: batch must be sorted (it descends %d times)" % layout.unsorted)
+    x = _f32_2d(x, "x")
+    if x.shape[0] != layout.n or x.shape[1] < 1:
+        raise ValueError("mi355_mp: x must be [%d, >= 1] for this batch layout (got %s)" % (layout.n, tuple(x.shape)))
+    return _ToDenseBatch.apply(x.contiguous(), layout, float(fill_value))
+
+
+def to_dense_adj(edge_index, layout, batch=None, edge_attr=None):
+    """[B, max_n, max_n] float32 with 1 per edge, or [B, max_n, max_n, D] holding
+    edge_attr [E, D] (float32; of several edges of one cell the last in edge
+    order wins), under the BatchLayout of the sorted batch vector `batch` (None =
+    one graph): mp_to_dense_adj_f32.  Not differentiable."""
+    nat = _lib.native()
+    _lib.require_device(edge_index, layout.starts, batch, edge_attr)
+    if layout.unsorted:
+        raise ValueError("mi355_mp: batch must be sorted (it descends %d times)" % layout.unsorted)
+    if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.shape[0] != 2:
+        raise ValueError("mi355_mp: edge_index must be int64 [2, E] (got %s %s)"
+                         % (edge_index.dtype, tuple(edge_index.shape)))
+    B, Nmax, n = layout.n_graphs, layout.max_n, layout.n
+    if batch is None and B > 1:
+        raise ValueError("mi355_mp: to_dense_adj needs the batch vector of a layout of %d graphs" % B)
+    row, col = edge_index[0].contiguous(), edge_index[1].contiguous()
+    E = row.shape[0]
+    D = 0
+    if edge_attr is not None:
+        if edge_attr.dtype != torch.float32 or edge_attr.dim() != 2 or edge_attr.shape[0] != E \
+                or edge_attr.shape[1] < 1:
+            raise ValueError("mi355_mp: edge_attr must be float32 [%d, >= 1] (got %s %s)"
+                             % (E, edge_attr.dtype, tuple(edge_attr.shape)))
+        edge_attr = edge_attr.detach().contiguous()
+        D = edge_attr.shape[1]
+    dev = edge_index.device
+    out = torch.empty((B, Nmax, Nmax) + ((D,) if D else ()), dtype=torch.float32, device=dev)
+    wsb = nat.mp_to_dense_adj_workspace(B, Nmax, D)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    _count_call(nat, "mp_to_dense_adj_f32", _lib.ptr(row if E else None), _lib.ptr(col if E else None), E,
+                _lib.ptr(edge_attr), D, _lib.ptr(None if batch is None else batch.contiguous()), n,
+                layout.starts.data_ptr(), B, Nmax, _lib.ptr(out if out.numel() else None), _lib.nbytes(out),
+                ws.data_ptr(), wsb, _lib.stream_ptr(dev))
+    return out

@@ -5,7 +5,9 @@ downloads, transforms).  What the reference's multi-GPU path needs is kept:
 ``Data`` (attribute container), ``Batch.from_data_list`` (block-diagonal
 mini-batch: node tensors concatenated, ``edge_index`` offset by the running
 node count, a ``batch`` vector of graph ids), ``DataLoader`` (yields
-``Batch``) and ``DataListLoader`` (yields lists, for ``nn.DataParallel``).
+``Batch``), ``DataListLoader`` (yields lists, for ``nn.DataParallel``) and
+``DenseDataLoader`` (stacks graphs of one size, as ``transforms.ToDense`` leaves
+them, along a new leading dimension).
 Callers: /root/reference/ConvexPruning.py:12,460-517,530 and
 /root/reference/examples/data_parallel.py:25-49.
 
@@ -18,7 +20,7 @@ import re
 import torch
 import torch.utils.data
 
-__all__ = ["Data", "Batch", "DataLoader", "DataListLoader"]
+__all__ = ["Data", "Batch", "DataLoader", "DataListLoader", "DenseDataLoader"]
 
 
 class Data(object):
@@ -332,3 +334,27 @@ class DataListLoader(torch.utils.data.DataLoader):
     def __init__(self, dataset, batch_size=1, shuffle=False, **kwargs):
         super(DataListLoader, self).__init__(dataset, batch_size, shuffle,
                                              collate_fn=lambda data_list: data_list, **kwargs)
+
+
+def _dense_collate(data_list):
+    batch = Batch()
+    for key in data_list[0].keys:
+        items = [d[key] for d in data_list]
+        first = items[0]
+        if torch.is_tensor(first):
+            batch[key] = torch.stack(items, dim=0)
+        elif isinstance(first, (int, float)):
+            batch[key] = torch.tensor(items)
+        else:
+            batch[key] = items
+    return batch
+
+
+class DenseDataLoader(torch.utils.data.DataLoader):
+    """Mini-batches of dense graphs of one size (``adj`` [N, N], ``x`` [N, F],
+    ``mask`` [N], as ``transforms.ToDense(num_nodes)`` makes them): every key is
+    stacked along a new leading dimension into one ``Batch``, which has no
+    ``batch`` vector."""
+
+    def __init__(self, dataset, batch_size=1, shuffle=False, **kwargs):
+        super(DenseDataLoader, self).__init__(dataset, batch_size, shuffle, collate_fn=_dense_collate, **kwargs)

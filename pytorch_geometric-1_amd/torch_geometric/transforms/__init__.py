@@ -1,6 +1,7 @@
 """torch_geometric.transforms (PyG 1.4.3): the transforms the example models
 need: Cartesian (SplineConv's pseudo-coordinates), Distance (the QM9 NNConv
-example's edge attribute) and Compose."""
+example's edge attribute), ToDense (the DiffPool example's dense graphs) and
+Compose."""
 import torch
 
 
@@ -90,4 +91,54 @@ class Compose(object):
         return "{}([\n{}\n])".format(self.__class__.__name__, "\n".join(args))
 
 
-__all__ = ["Cartesian", "Distance", "Compose"]
+class ToDense(object):
+    r"""Converts a sparse graph to a dense one: ``data.adj`` [n, n] (or [n, n, D]
+    from ``edge_attr``) replaces ``edge_index`` and ``edge_attr``, ``data.mask``
+    (bool [n]) marks the graph's own nodes, and ``x``, ``pos`` and a node-level
+    ``y`` are padded with zeros to ``num_nodes`` rows.
+
+    Args:
+        num_nodes (int, optional): the padded node count; None keeps the
+            graph's own. (default: None)
+    """
+
+    def __init__(self, num_nodes=None):
+        self.num_nodes = num_nodes
+
+    def __call__(self, data):
+        assert data.edge_index is not None
+        orig_num_nodes = data.num_nodes
+        if self.num_nodes is None:
+            num_nodes = orig_num_nodes
+        else:
+            assert orig_num_nodes <= self.num_nodes
+            num_nodes = self.num_nodes
+        edge_attr = data.edge_attr
+        if edge_attr is None:
+            edge_attr = torch.ones(data.edge_index.size(1), dtype=torch.float)
+        adj = torch.zeros((num_nodes, num_nodes) + tuple(edge_attr.shape[1:]), dtype=edge_attr.dtype)
+        adj[data.edge_index[0], data.edge_index[1]] = edge_attr
+        data.adj = adj
+        data.edge_index = None
+        data.edge_attr = None
+        data.mask = torch.zeros(num_nodes, dtype=torch.bool)
+        data.mask[:orig_num_nodes] = True
+
+        def pad(t):
+            size = [num_nodes - t.size(0)] + list(t.size())[1:]
+            return torch.cat([t, t.new_zeros(size)], dim=0)
+        if data.x is not None:
+            data.x = pad(data.x)
+        if data.pos is not None:
+            data.pos = pad(data.pos)
+        if data.y is not None and torch.is_tensor(data.y) and data.y.dim() >= 1 and data.y.size(0) == orig_num_nodes:
+            data.y = pad(data.y)
+        return data
+
+    def __repr__(self):
+        if self.num_nodes is None:
+            return "{}()".format(self.__class__.__name__)
+        return "{}(num_nodes={})".format(self.__class__.__name__, self.num_nodes)
+
+
+__all__ = ["Cartesian", "Distance", "ToDense", "Compose"]

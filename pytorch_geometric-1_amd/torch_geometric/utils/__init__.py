@@ -7,7 +7,8 @@ from .degree import degree
 from .get_laplacian import get_laplacian
 from .repeat import repeat
 from .normalized_cut import normalized_cut
+from .to_dense import to_dense_batch, to_dense_adj
 
 __all__ = ["maybe_num_nodes", "scatter_", "softmax", "contains_self_loops", "remove_self_loops",
            "add_self_loops", "add_remaining_self_loops", "degree", "get_laplacian", "repeat",
-           "normalized_cut"]
+           "normalized_cut", "to_dense_batch", "to_dense_adj"]
