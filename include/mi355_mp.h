@@ -1409,6 +1409,71 @@ int64_t mp_to_dense_adj_f32(const int64_t* row, const int64_t* col, int64_t E, c
                             const int64_t* batch, int64_t n, const int64_t* starts, int64_t B, int64_t Nmax,
                             float* out, size_t out_bytes, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Link prediction: GAE / VGAE decoder, loss and negative sampler (csrc/mp_link.hip)
+ * PyG 1.4.x's InnerProductDecoder [U] scores an edge list as (z[row] * z[col]).sum(1)
+ * over two [E, C] gathers, GAE.recon_loss takes -log(sigmoid + 1e-15) means of it, and
+ * utils.negative_sampling draws on the host and retries.  These calls keep no [E, C]
+ * array, use no float atomics and read nothing back.
+ *   row, col [E] int64 in any order (repeats and row == col allowed), z [N, ldz] fp32 with
+ *   C >= 1 columns used, ldz >= C.  An edge with an end outside [0, N) reads nothing
+ *   and scores NaN.  A group of G lanes serves one edge: G = mp_link_lanes(C, vec4), the
+ *   power of two covering C / 4 lanes of 16-byte loads, at most 16 (vec4: C % 4 == 0,
+ *   ldz % 4 == 0 and z 16-byte aligned), or C scalar lanes, at most 64, looping beyond;
+ *   `lanes` overrides it (0 = that rule; else a power of two up to 64).  Each lane adds its
+ *   columns' products in column order and the group adds its lanes in a fixed tree, so
+ *   v[e] depends on C, the mapping and the two rows only.
+ *
+ * mp_edge_score_f32: v[e] = sum_c z[row_e, c] * z[col_e, c], or its sigmoid
+ *   1 / (1 + expf(-v)).
+ * mp_link_loss_f32: one side of the reconstruction loss.  With p = 1 / (1 + expf(-v_e))
+ *   and EPS = 1e-15f, in fp32: positive = 1: t_e = -logf(p + EPS), coef[e] = -p (1 - p) /
+ *   (p + EPS) / E; positive = 0: t_e = -logf(1 - p + EPS), coef[e] = p (1 - p) / (1 - p +
+ *   EPS) / E -- coef[e] is d(mean t) / dv_e, so a backward never forms v again.  1 - p
+ *   is evaluated as 1 / (1 + expf(v_e)): the same quantity, without the cancellation
+ *   of the fp32 subtraction once p nears 1.  The t_e
+ *   are added in fp64 in a fixed order (per-block partials in ws, one block adds them by
+ *   index) and loss[0] is the mean, rounded once to fp32; E = 0 gives nan.
+ *   ws: mp_link_loss_workspace(E) bytes (csrc/mp_link.hip LinkLossWs), 16-byte aligned.
+ * mp_link_grad_rows_f32: dz[r, :] = (init_from_out ? dz[r, :] : 0) + sum over the slots s
+ *   of row r, in slot order, of coef[eid[s] mod n_coef] * z[col[s], :] over the rowptr /
+ *   col / eid of mp_csr_build -- no schedule and no read of its bad-index count are
+ *   needed; a slot whose column is outside [0, N) is skipped.  One lane group walks a
+ *   row.  With the CSR built over the 2 E entries key = [row | col], other = [col | row]
+ *   and n_coef = E this is the whole gradient of z of a score or a loss over (row,
+ *   col): dz[i] = sum_{row_e = i} coef_e z[col_e] + sum_{col_e = i} coef_e z[row_e].
+ *   n_slots / 2 <= n_coef <= n_slots.
+ * mp_neg_sample: n_samples draws, with replacement, from the keys in [0, T) that are
+ *   NOT in the sorted distinct table keys[0..U), U = n_keys[0] read on the device (at
+ *   most keys_bytes / 8).  mode 0: key = row * N + col, T = N * N; mode 1: the strict
+ *   upper triangle, key = j (j - 1) / 2 + i for i < j, T = N (N - 1) / 2.  Draw s takes
+ *   r = mulhi64(h, T - U) with h = mix(mix(seed) ^ s), mix the splitmix64 finaliser,
+ *   finds the smallest j with keys[j] - j > r by binary search and returns key r + j:
+ *   uniform over the non-edges, exact, and one search whatever the density.  mode 0
+ *   writes out_row / out_col [n_samples]; mode 1 writes [2 n_samples], the pair then
+ *   its mirror: out_row = [i | j], out_col = [j | i].  With T - U <= 0 every entry is -1.
+ * mp_neg_sample_rows: for edge e with i = row[e], the r-th column missing from row i's
+ *   keys (mode 0's table; two lower bounds give the row's d_i keys), r = mulhi64(h(seed,
+ *   e), N - d_i).  A full row (d_i = N) or an i outside [0, N) gives -1.
+ * N <= 3037000499 (N * N below 2^63).  Every call returns the launches enqueued, >= 0,
+ * or -(MP_ERR_* code) with the reason in mp_last_error(), for a bad argument before
+ * any launch; mp_link_lanes answers a question (or -MP_ERR_ARG for C < 1). */
+int64_t mp_link_lanes(int32_t C, int32_t vec4);
+int64_t mp_edge_score_f32(const int64_t* row, const int64_t* col, int64_t E, const float* z, int64_t ldz, int64_t N,
+                          int32_t C, int32_t sigmoid, int32_t lanes, float* v, size_t v_bytes, void* stream);
+size_t mp_link_loss_workspace(int64_t E);
+int64_t mp_link_loss_f32(const int64_t* row, const int64_t* col, int64_t E, const float* z, int64_t ldz, int64_t N,
+                         int32_t C, int32_t positive, int32_t lanes, float* coef, size_t coef_bytes, float* loss,
+                         size_t loss_bytes, void* ws, size_t ws_bytes, void* stream);
+int64_t mp_link_grad_rows_f32(const int32_t* rowptr, const int32_t* col, const int32_t* eid, int64_t n_rows,
+                              int64_t n_slots, const float* coef, int64_t n_coef, const float* z, int64_t ldz,
+                              int64_t N, int32_t C, int32_t init_from_out, float* dz, int64_t lddz, size_t dz_bytes,
+                              void* stream);
+int64_t mp_neg_sample(const int64_t* keys, size_t keys_bytes, const int64_t* n_keys, int64_t N, int32_t mode,
+                      uint64_t seed, int64_t n_samples, int64_t* out_row, int64_t* out_col, size_t out_bytes,
+                      void* stream);
+int64_t mp_neg_sample_rows(const int64_t* keys, size_t keys_bytes, const int64_t* n_keys, int64_t N, uint64_t seed,
+                           const int64_t* row, int64_t E, int64_t* out, size_t out_bytes, void* stream);
+
 /* ---- other dtypes (csrc/mp_dtype.hip) -------------------------------------
  * torch_scatter 2.0.4 reduces any dtype ([U8/U9]); the fp32 hot path is
  * mp_aggregate_f32, these are the breadth path for the rest. */

@@ -265,7 +265,17 @@ SIGNATURES = {
     "mp_to_dense_batch_bwd_f32": (i64, [c_p, i64, i32, c_p, i64, i64, c_p, sz, c_p]),
     "mp_to_dense_adj_workspace": (sz, [i64, i64, i32]),
     "mp_to_dense_adj_f32": (i64, [c_p, c_p, i64, c_p, i32, c_p, i64, c_p, i64, i64, c_p, sz, c_p, sz, c_p]),
+    # link prediction (csrc/mp_link.hip): int64 returns again, the sign tested by ops._count_call
+    "mp_link_lanes": (i64, [i32, i32]),            # lanes per edge of a width, or -MP_ERR_ARG
+    "mp_edge_score_f32": (i64, [c_p, c_p, i64, c_p, i64, i64, i32, i32, i32, c_p, sz, c_p]),
+    "mp_link_loss_workspace": (sz, [i64]),
+    "mp_link_loss_f32": (i64, [c_p, c_p, i64, c_p, i64, i64, i32, i32, i32, c_p, sz, c_p, sz, c_p, sz, c_p]),
+    "mp_link_grad_rows_f32": (i64, [c_p, c_p, c_p, i64, i64, c_p, i64, c_p, i64, i64, i32, i32, c_p, i64, sz, c_p]),
+    "mp_neg_sample": (i64, [c_p, sz, c_p, i64, i32, u64, i64, c_p, c_p, sz, c_p]),
+    "mp_neg_sample_rows": (i64, [c_p, sz, c_p, i64, u64, c_p, i64, c_p, sz, c_p]),
 }
+MP_NEG_FULL = 0
+MP_NEG_UPPER = 1
 
 # Of the symbols declared `int` / `int32_t`, these answer a question (a version,
 # a count, a yes / no); every other one returns a status: MP_OK, or a code with

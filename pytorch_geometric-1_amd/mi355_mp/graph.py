@@ -394,7 +394,29 @@ def in_csr_order(csr, edge_values):
     return val[1]
 
 
+class KeyTable:
+    """The sorted distinct int64 keys of the edges a negative sampler must not
+    return (mp_neg_sample's table): keys [U] and n_keys [1] on the device, U and
+    the edge count the sample-count cap uses (n_edges) on the host."""
+
+    def __init__(self, keys, n_edges, n_nodes, upper):
+        self.keys = keys.contiguous()
+        self.count = int(keys.numel())
+        self.n_keys = torch.full((1,), self.count, dtype=torch.int64, device=keys.device)
+        self.n_edges, self.n_nodes, self.upper = int(n_edges), int(n_nodes), bool(upper)
+
+
+_key_cache = _Cache()
+
+
+def key_table_for(edge_index, extra, factory):
+    """Cached KeyTable of an edge_index tensor: built once per tensor (factory),
+    rebuilt if it is modified in place, dropped with it -- as graph_for's CSRs."""
+    return _key_cache.get(edge_index, extra, factory)
+
+
 def clear_caches():
     _graph_cache.clear()
     _index_cache.clear()
     _order_cache.clear()
+    _key_cache.clear()

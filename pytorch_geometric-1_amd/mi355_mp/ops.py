@@ -461,9 +461,9 @@ def index_range(idx):
 def forget_index(idx):
     """Drop every cached fact about idx (its range and CSR graphs): for index
     tensors written behind autograd's back (see index_range)."""
-    from .graph import _graph_cache, _index_cache
+    from .graph import _graph_cache, _index_cache, _key_cache
     base = idx._base if idx._base is not None else idx
-    for c in (_range_cache, _graph_cache, _index_cache):
+    for c in (_range_cache, _graph_cache, _index_cache, _key_cache):
         c._drop(id(base))
 
 
@@ -3696,4 +3696,265 @@ def to_dense_adj(edge_index, layout, batch=None, edge_attr=None):
                 _lib.ptr(edge_attr), D, _lib.ptr(None if batch is None else batch.contiguous()), n,
                 layout.starts.data_ptr(), B, Nmax, _lib.ptr(out if out.numel() else None), _lib.nbytes(out),
                 ws.data_ptr(), wsb, _lib.stream_ptr(dev))
+    return out
+
+
+# ---------------------------------------------------------------------------
+# link prediction: edge scores, the reconstruction loss, negative sampling
+# (csrc/mp_link.hip; PyG 1.4.x nn.models.autoencoder, utils.negative_sampling [U])
+# ---------------------------------------------------------------------------
+
+def link_lanes(C, vec4=True):
+    """Lanes that serve one edge of a z of C columns (mp_link_lanes): the power of
+    two covering C / 4 lanes of 16-byte loads, at most 16 (vec4 and C % 4 == 0), or
+    C scalar lanes, at most 64."""
+    return int(_count_call(_lib.load(), "mp_link_lanes", int(C), int(bool(vec4))))
+
+
+def _link_args(z, edge_index, what, trusted=False):
+    """(z, row, col) of a scoring call: z float32 [N, C >= 1] with unit column
+    stride, edge_index int64 [2, E] within [0, N) (check_row_index: one read the
+    first time a tensor is seen; trusted: the sampler's own output)."""
+    _lib.require_device(z, edge_index)
+    z = _f32_2d(z, "z")
+    if z.shape[1] < 1:
+        raise ValueError("mi355_mp: z must have at least one column (got %s)" % (tuple(z.shape),))
+    if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.shape[0] != 2:
+        raise ValueError("mi355_mp: edge_index must be int64 [2, E] (got %s %s)"
+                         % (edge_index.dtype, tuple(edge_index.shape)))
+    if not trusted:
+        check_row_index(edge_index, z.shape[0], what)
+    return z, edge_index[0].contiguous(), edge_index[1].contiguous()
+
+
+def edge_score_forward(z, row, col, sigmoid=False, lanes=0):
+    """v [E] of mp_edge_score_f32 (no autograd, no checks: see edge_score)."""
+    nat = _lib.native()
+    E = row.numel()
+    v = torch.empty(E, dtype=torch.float32, device=z.device)
+    if E:
+        _count_call(nat, "mp_edge_score_f32", row.data_ptr(), col.data_ptr(), E, z.data_ptr(), z.stride(0), z.shape[0],
+                    z.shape[1], int(bool(sigmoid)), int(lanes), v.data_ptr(), _lib.nbytes(v), _lib.stream_ptr(z.device))
+    return v
+
+
+def link_loss_side(z, row, col, positive, lanes=0):
+    """(loss [], coef [E]) of mp_link_loss_f32: the mean of -log(p + EPS)
+    (positive) or -log(1 - p + EPS) over the edges, p the sigmoid of the score,
+    and coef[e] = d loss / d v_e (no autograd, no checks: see link_loss)."""
+    nat = _lib.native()
+    dev = z.device
+    E = row.numel()
+    coef = torch.empty(E, dtype=torch.float32, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    wsb = nat.mp_link_loss_workspace(E)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    _count_call(nat, "mp_link_loss_f32", _lib.ptr(row if E else None), _lib.ptr(col if E else None), E, z.data_ptr(),
+                z.stride(0), z.shape[0], z.shape[1], int(bool(positive)), int(lanes), _lib.ptr(coef if E else None),
+                _lib.nbytes(coef), loss.data_ptr(), 4, ws.data_ptr(), wsb, _lib.stream_ptr(dev))
+    return loss[0], coef
+
+
+def link_pair_csr(row, col, n):
+    """(rowptr, col, eid) int32 of mp_csr_build over the 2 E entries key = [row |
+    col], other = [col | row]: node i's slots name, in edge order, the other end of
+    every edge i is an end of (eid >= E: as its col).  Unscheduled, and the build's
+    bad-index count is not read: no host read (the caller vouches for the range)."""
+    nat = _lib.native()
+    dev = row.device
+    E2 = 2 * row.numel()
+    key, other = torch.cat([row, col]), torch.cat([col, row])
+    rowptr = torch.empty(n + 1, dtype=torch.int32, device=dev)
+    c = torch.empty(max(E2, 1), dtype=torch.int32, device=dev)
+    eid = torch.empty(max(E2, 1), dtype=torch.int32, device=dev)
+    bad = torch.empty(1, dtype=torch.int32, device=dev)
+    wsb = nat.mp_csr_build_workspace(E2, n)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    nat.mp_csr_build(key.data_ptr(), other.data_ptr(), E2, n, n, rowptr.data_ptr(), c.data_ptr(), eid.data_ptr(),
+                     bad.data_ptr(), ws.data_ptr(), wsb, _lib.stream_ptr(dev))
+    return rowptr, c, eid, E2
+
+
+def link_grad_rows(pair_csr, coef, z, out=None):
+    """dz [N, C] (+= when out is given) = sum_{row_e = i} coef_e z[col_e] + sum_{col_e
+    = i} coef_e z[row_e] over link_pair_csr's slots (mp_link_grad_rows_f32)."""
+    nat = _lib.native()
+    rowptr, c, eid, E2 = pair_csr
+    N, C = z.shape
+    init = out is not None
+    if out is None:
+        out = torch.empty((N, C), dtype=torch.float32, device=z.device)
+    if N:
+        _count_call(nat, "mp_link_grad_rows_f32", rowptr.data_ptr(), c.data_ptr(), eid.data_ptr(), N, E2,
+                    _lib.ptr(coef if E2 else None), E2 // 2, _lib.ptr(z if E2 else None), z.stride(0), N, C, int(init),
+                    out.data_ptr(), out.stride(0), _extent_bytes(out), _lib.stream_ptr(z.device))
+    return out
+
+
+def link_grad_engine(graph, coef, z, out=None):
+    """The same gradient on the aggregation engine, for a cached edge list (graph =
+    graph_for(edge_index, N, N)): two weighted row sums, over graph.dst then
+    graph.src, the second into the first's output."""
+    init = _lib.MP_FLAG_INIT_FROM_OUT if out is not None else 0
+    if coef.numel() == 0:
+        return out if out is not None else torch.zeros(z.shape, dtype=torch.float32, device=z.device)
+    dst, src = graph.dst, graph.src
+    out, _ = _aggregate(dst, "other", z, dst.to_csr_order(coef), "sum", init, None, out=out)
+    _aggregate(src, "other", z, src.to_csr_order(coef), "sum", _lib.MP_FLAG_INIT_FROM_OUT, None, out=out)
+    return out
+
+
+def _link_grad(z, edge_index, row, col, coef, cached, out=None):
+    from .graph import graph_for
+    n = z.shape[0]
+    if cached:
+        return link_grad_engine(graph_for(edge_index, n, n), coef, z, out)
+    return link_grad_rows(link_pair_csr(row, col, n), coef, z, out)
+
+
+class _EdgeScore(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, edge_index, row, col, sigmoid, cached):
+        v = edge_score_forward(z, row, col, sigmoid)
+        ctx.save_for_backward(z, edge_index, row, col, v)
+        ctx.sigmoid, ctx.cached = sigmoid, cached
+        return v
+
+    @staticmethod
+    def backward(ctx, g):
+        z, edge_index, row, col, v = ctx.saved_tensors
+        coef = g.to(torch.float32).contiguous()
+        if ctx.sigmoid:
+            coef = coef * (v * (1.0 - v))
+        return _link_grad(z, edge_index, row, col, coef, ctx.cached), None, None, None, None, None
+
+
+def edge_score(z, edge_index, sigmoid=False, cached=True):
+    """v[e] = <z[row_e], z[col_e]> (or its sigmoid) for an int64 [2, E] edge list
+    in any order, differentiable in z: InnerProductDecoder.forward without the two
+    [E, C] gathers.  The backward sums coef_e z[other end] per node in edge order,
+    deterministic and without float atomics: on the aggregation engine over the
+    edge list's cached CSRs (cached=True: graph_for, one host read the first
+    time the tensor is seen), or over an unscheduled CSR built on the spot with no
+    host read (cached=False: edge lists that are new every step)."""
+    z, row, col = _link_args(z, edge_index, "edge_score")
+    return _EdgeScore.apply(z, edge_index, row, col, bool(sigmoid), bool(cached))
+
+
+class _LinkLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, pos, prow, pcol, nrow, ncol):
+        lp, cp = link_loss_side(z, prow, pcol, True)
+        ln, cn = link_loss_side(z, nrow, ncol, False)
+        ctx.save_for_backward(z, pos, prow, pcol, nrow, ncol, cp, cn)
+        return lp + ln
+
+    @staticmethod
+    def backward(ctx, g):
+        z, pos, prow, pcol, nrow, ncol, cp, cn = ctx.saved_tensors
+        g = g.to(torch.float32)
+        dz = _link_grad(z, pos, prow, pcol, cp * g, True)
+        if nrow.numel():
+            dz = _link_grad(z, None, nrow, ncol, cn * g, False, out=dz)
+        return dz, None, None, None, None, None
+
+
+def link_loss(z, pos_edge_index, neg_edge_index, neg_trusted=False):
+    """GAE's reconstruction loss with the inner-product decoder, fused:
+    mean(-log(sigmoid(v_pos) + 1e-15)) + mean(-log(1 - sigmoid(v_neg) + 1e-15)), one
+    pass per side that also writes d loss / d v_e, each mean carried in fp64 in a
+    fixed order.  The backward never forms the scores again: the positive edges go
+    through the engine over pos_edge_index's cached CSRs, the negative ones --
+    new every step -- through an unscheduled CSR (mp_link_grad_rows_f32), scaled by
+    the incoming gradient on the device.  An empty side gives nan, as upstream's
+    mean of nothing.  neg_trusted: the negatives come from negative_sample and need
+    no range check (no host read)."""
+    z, prow, pcol = _link_args(z, pos_edge_index, "link_loss")
+    _, nrow, ncol = _link_args(z, neg_edge_index, "link_loss", trusted=neg_trusted)
+    return _LinkLoss.apply(z, pos_edge_index, prow, pcol, nrow, ncol)
+
+
+def _key_table(edge_index, n, upper=False, loops=False):
+    """The cached KeyTable (graph.key_table_for) of the pairs a sampler over
+    edge_index must not return.  upper: the undirected pairs i < j as j (j - 1) / 2
+    + i; else row * n + col, with every (i, i) added when loops (the edge list
+    GAE.recon_loss samples against: self loops removed, then one per node).  Built
+    with a key sort and a dedupe, reading the table's size (and the loop count)
+    once per edge_index tensor."""
+    from .graph import KeyTable, key_table_for
+    _lib.require_device(edge_index)
+    if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.shape[0] != 2:
+        raise ValueError("mi355_mp: edge_index must be int64 [2, E] (got %s %s)"
+                         % (edge_index.dtype, tuple(edge_index.shape)))
+    n = int(n)
+    if n < 0 or n > 3037000499:
+        raise ValueError("mi355_mp: num_nodes = %d is outside [0, 3037000499]" % n)
+    check_row_index(edge_index, n, "negative_sampling")
+
+    def build():
+        row, col = edge_index[0], edge_index[1]
+        n_edges = row.numel()
+        if upper:
+            keep = row != col
+            lo, hi = torch.minimum(row, col)[keep], torch.maximum(row, col)[keep]
+            key = ((hi * (hi - 1)) >> 1) + lo
+        else:
+            key = row * n + col
+            if loops:
+                n_edges += n - int((row == col).sum())
+                ar = torch.arange(n, dtype=torch.int64, device=row.device)
+                key = torch.cat([key, ar * n + ar])
+        return KeyTable(torch.unique(key), n_edges, n, upper)
+    return key_table_for(edge_index, ("keys", n, bool(upper), bool(loops)), build)
+
+
+def _sample_seed(seed, device):
+    return dropout_seed(device) if seed is None else int(seed) & _MASK64
+
+
+def negative_sample(edge_index, num_nodes, num_neg_samples=None, force_undirected=False, seed=None, loops=False):
+    """[2, n] int64 pairs that are not edges of edge_index, drawn uniformly WITH
+    replacement (upstream's first round draws without; a pair can repeat here)
+    by mp_neg_sample: draw s is the r-th key outside the cached sorted key table,
+    r = mulhi64(mix(mix(seed) ^ s), #non-edges) -- no rejection loop, no retry,
+    nothing read back.  n = min(num_neg_samples or E, N^2 - E), E the edge count
+    (after the loop rewrite when loops: see _key_table); force_undirected draws n
+    // 2 pairs i < j of the strict upper triangle that are in neither direction
+    and returns them with their mirrors, [i | j ; j | i].  When no pair is
+    missing the result is empty.  seed: None takes dropout_seed(device), so
+    torch.cuda.manual_seed repeats the sequence."""
+    nat = _lib.native()
+    table = _key_table(edge_index, num_nodes, upper=force_undirected, loops=loops)
+    dev = edge_index.device
+    N, E = table.n_nodes, table.n_edges
+    n = max(min(int(num_neg_samples or E), N * N - E), 0)
+    if force_undirected:
+        n //= 2
+    total = N * (N - 1) // 2 if force_undirected else N * N
+    if total - table.count <= 0:
+        n = 0
+    cols = 2 * n if force_undirected else n
+    out = torch.empty((2, cols), dtype=torch.int64, device=dev)
+    if n:
+        _count_call(nat, "mp_neg_sample", _lib.ptr(table.keys if table.count else None), _lib.nbytes(table.keys),
+                    table.n_keys.data_ptr(), N, _lib.MP_NEG_UPPER if force_undirected else _lib.MP_NEG_FULL,
+                    _sample_seed(seed, dev), n, out[0].data_ptr(), out[1].data_ptr(), cols * 8, _lib.stream_ptr(dev))
+    return out
+
+
+def structured_negative_sample(edge_index, num_nodes, seed=None):
+    """k [E] int64: for every edge (i, j) a node k with (i, k) not an edge, uniform
+    over row i's missing columns (mp_neg_sample_rows; with replacement across
+    edges, as upstream).  A node linked to every node has no such k: its edges get
+    -1, where upstream's rejection loop would never end."""
+    nat = _lib.native()
+    table = _key_table(edge_index, num_nodes)
+    dev = edge_index.device
+    row = edge_index[0].contiguous()
+    E = row.numel()
+    out = torch.empty(E, dtype=torch.int64, device=dev)
+    if E:
+        _count_call(nat, "mp_neg_sample_rows", _lib.ptr(table.keys if table.count else None), _lib.nbytes(table.keys),
+                    table.n_keys.data_ptr(), table.n_nodes, _sample_seed(seed, dev), row.data_ptr(), E, out.data_ptr(),
+                    E * 8, _lib.stream_ptr(dev))
     return out
