@@ -729,6 +729,73 @@ int64_t mp_nnconv_edge_grad_f32(const int64_t* rows, const int64_t* cols, int64_
                                 int64_t lddz, const float* x, int64_t ldx, int32_t H, int32_t Cin, float* dh,
                                 int64_t lddh, size_t dh_bytes, void* stream);
 
+/* ---- GMMConv: Gaussian mixture weights fused into the aggregation (csrc/mp_gmm.hip)
+ * PyG 1.4.3's nn.conv.GMMConv [U] with shared Gaussians: per edge e = (j -> i)
+ * with pseudo-coordinates p_e in R^D,
+ *   w_k(p) = exp(sum_d -0.5 (p_d - mu_kd)^2 * iv_kd),   iv_kd = 1 / (1e-15f + sigma_kd^2)
+ *   m_e    = sum_k w_k(p_e) * Y[j, k, :],               Y = (x g).view(N, K, M)
+ * The weights are evaluated inside the segmented pass from the D floats of
+ * pseudo[e]: neither the [E, K, M] gathered operand nor an [E, K] coefficient
+ * array exists.  With G'[(k, c), m] = g[c, k*M + m]:
+ *   sum_{e -> i} m_e = (sum_{e -> i} w(p_e) (x) x_j) G'
+ * pseudo is [n_p_edges, ldp >= D] fp32 in ORIGINAL edge order, read through
+ * g->eid; n_p_edges must cover the edge-id space of g (g->n_ids, or g->n_edges
+ * when that is 0).  mu and sigma are [K, D] fp32, contiguous.
+ * Limits (mp_gmm_ok != 0; needs no GPU): K, D, Cin, Cout >= 1, K * D <= 1024
+ * (the mu / iv table a workgroup stages in LDS: 8 KiB) and K * Cin, K * Cout <=
+ * 2^20 floats (one row of Z or Y).  The aggregate calls apply the limits to
+ * their own (K, D, Cin) or (K, D, F).
+ * Both aggregate calls walk g->rowptr / col / eid only (col and eid required),
+ * one owner per output entry visits its row's slots in slot order and adds
+ * left to right (gather: k = 0..K-1 inside a slot): fp32, deterministic, no
+ * atomics.  Hub rows are not split.  Every output entry of every row is
+ * written exactly once (zeros for rows without slots); padding beyond it is
+ * left untouched.
+ *   mp_gmm_aggregate_bins_f32 (x [n_cols, ldx >= Cin]):
+ *     out[r, k*Cin + c] = scale[r] * sum_{slots of r} w_k(pseudo[eid[slot]]) * x[col[slot], c]
+ *     ldo >= K * Cin.  Lanes run over the flattened (k, c) for Cin < 32, over c
+ *     with 16 values of k per lane from Cin = 32 on; there a wave evaluates the
+ *     weights of four slots cooperatively, one exp per (slot, k).
+ *   mp_gmm_aggregate_gather_f32 (y [n_cols, K, F], ldy >= K * F):
+ *     out[r, f] = scale[r] * sum_{slots of r} sum_k w_k(pseudo[eid[slot]]) * y[col[slot], k*F + f] (+ bias[f])
+ *     ldo >= F.  Lanes run over f; a row's lane group evaluates its (slot, k)
+ *     weights cooperatively.
+ *   mp_gmm_param_grad_f32 (rows / cols [n_edges] int64: each edge's row of dz and
+ *     of x, range-checked by the caller; pseudo [n_edges, ldp] indexed by the edge
+ *     itself; dz [.., lddz >= K * Cin]): with dw[e, k] = sum_c dz[rows[e], k*Cin + c]
+ *     * x[cols[e], c] and t = dw * w_k(pseudo[e]) (w recomputed),
+ *       dmu[k, d]     = sum_e t * (p_d - mu_kd) * iv_kd
+ *       dsigma[k, d]  = sum_e t * ((p_d - mu_kd)^2 * iv_kd) * (sigma_kd * iv_kd)
+ *       dpseudo[e, d] = -sum_k t * (p_d - mu_kd) * iv_kd   (dpseudo may be NULL: not written; lddp >= D)
+ *     dmu, dsigma [K, D] contiguous, every entry written (zeros without edges).
+ *     The association of dsigma keeps every factor finite wherever w != 0, and
+ *     an (edge, k) whose weight underflows to 0 contributes EXACTLY zero to all
+ *     three -- upstream's autograd yields NaN there (0 * inf) when sigma is
+ *     tiny.  Stage 1: one workgroup per chunk of mp_gmm_grad_chunk(n_edges, K, D)
+ *     edges sums its 2 K D partials in a fixed order into ws; stage 2 adds the
+ *     partials in chunk order.  The chunk is a pure function of (n_edges, K, D):
+ *     at least 1024 edges, at most 4096 chunks and 8 MiB of partials, so the
+ *     result does not depend on grid size or occupancy.  ws:
+ *     mp_gmm_param_grad_workspace(n_edges, K, D) bytes, checked before any launch.
+ * row_scale [n_rows] or NULL (= 1), bias [F] or NULL.
+ * Additions to ABI 7 that return int64_t like the NNConv calls: the launches
+ * enqueued, >= 0, or -(MP_ERR_* code) with the reason in mp_last_error(); a bad
+ * argument is refused before any launch. */
+int64_t mp_gmm_ok(int32_t K, int32_t D, int32_t Cin, int32_t Cout);
+int64_t mp_gmm_aggregate_bins_f32(const mp_csr* g, const float* pseudo, int64_t n_p_edges, int64_t ldp, int32_t D,
+                                  const float* mu, const float* sigma, int32_t K, const float* x, int64_t ldx,
+                                  int32_t Cin, const float* row_scale, float* out, int64_t ldo, void* stream);
+int64_t mp_gmm_aggregate_gather_f32(const mp_csr* g, const float* pseudo, int64_t n_p_edges, int64_t ldp, int32_t D,
+                                    const float* mu, const float* sigma, int32_t K, const float* y, int64_t ldy,
+                                    int32_t F, const float* row_scale, const float* bias, float* out, int64_t ldo,
+                                    void* stream);
+int64_t mp_gmm_grad_chunk(int64_t n_edges, int32_t K, int32_t D);
+size_t mp_gmm_param_grad_workspace(int64_t n_edges, int32_t K, int32_t D);
+int64_t mp_gmm_param_grad_f32(const int64_t* rows, const int64_t* cols, int64_t n_edges, const float* pseudo,
+                              int64_t ldp, int32_t D, const float* mu, const float* sigma, int32_t K, const float* dz,
+                              int64_t lddz, const float* x, int64_t ldx, int32_t Cin, float* dmu, float* dsigma,
+                              float* dpseudo, int64_t lddp, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- Attention readout: Set2Set / GlobalAttention (csrc/mp_glob.hip) ---------
  * PyG 1.4.3's nn.glob.Set2Set and nn.glob.GlobalAttention [U] share one step: a
  * softmax of one scalar per node over each graph, then the softmax-weighted sum

@@ -221,6 +221,16 @@ SIGNATURES = {
     "mp_nnconv_aggregate_gather_f32": (i64, [ctypes.POINTER(MpCsr), c_p, i64, i64, i32, c_p, i64, i32, c_p, c_p, c_p,
                                              i64, c_p]),
     "mp_nnconv_edge_grad_f32": (i64, [c_p, c_p, i64, c_p, i64, c_p, i64, i32, i32, c_p, i64, sz, c_p]),
+    # GMMConv (csrc/mp_gmm.hip): int64 returns like NNConv's, the sign tested by ops._count_call
+    "mp_gmm_ok": (i64, [i32, i32, i32, i32]),      # an answer (0 or 1), not a status
+    "mp_gmm_aggregate_bins_f32": (i64, [ctypes.POINTER(MpCsr), c_p, i64, i64, i32, c_p, c_p, i32, c_p, i64, i32, c_p,
+                                        c_p, i64, c_p]),
+    "mp_gmm_aggregate_gather_f32": (i64, [ctypes.POINTER(MpCsr), c_p, i64, i64, i32, c_p, c_p, i32, c_p, i64, i32,
+                                          c_p, c_p, c_p, i64, c_p]),
+    "mp_gmm_grad_chunk": (i64, [i64, i32, i32]),   # an answer (edges per chunk), or -MP_ERR_ARG
+    "mp_gmm_param_grad_workspace": (sz, [i64, i32, i32]),
+    "mp_gmm_param_grad_f32": (i64, [c_p, c_p, i64, c_p, i64, i32, c_p, c_p, i32, c_p, i64, c_p, i64, i32, c_p, c_p,
+                                    c_p, i64, c_p, sz, c_p]),
     # the attention readout (csrc/mp_glob.hip): int64 returns again, the sign tested by ops._count_call
     "mp_readout_path": (i64, [i64, i32]),          # an answer (0, 1 or 2), or -MP_ERR_ARG
     "mp_readout_chunk": (i64, [i32]),              # nodes per chunk of a split graph, or -MP_ERR_ARG

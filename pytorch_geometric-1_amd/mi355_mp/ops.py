@@ -1683,6 +1683,225 @@ def nnconv_propagate(graph, x, h, head_weight, head_bias, reduce, form=None, bia
 
 
 # ---------------------------------------------------------------------------
+# GMMConv: Gaussian mixture weights fused into the aggregation (csrc/mp_gmm.hip)
+# ---------------------------------------------------------------------------
+
+def gmm_ok(K, D, c_in, c_out):
+    """Whether (K, D, Cin, Cout) lies inside the fused path's limits (mp_gmm_ok; needs no GPU)."""
+    return bool(_lib.native().mp_gmm_ok(int(K), int(D), int(c_in), int(c_out)))
+
+
+def gmm_grad_chunk(n_edges, K, D):
+    """Edges per stage-1 workgroup of gmm_param_grad: a pure function of the shape
+    (mp_gmm_grad_chunk; needs no GPU)."""
+    c = int(_lib.native().mp_gmm_grad_chunk(int(n_edges), int(K), int(D)))
+    if c < 0:
+        raise ValueError("mi355_mp: " + _lib.native().mp_last_error().decode(errors="replace"))
+    return c
+
+
+def _gmm_table(mu, sigma):
+    if mu.dtype != torch.float32 or sigma.dtype != torch.float32 or mu.dim() != 2 or mu.shape != sigma.shape:
+        raise ValueError("mi355_mp: mu and sigma must be float32 [K, D] (got %s %s, %s %s)"
+                         % (mu.dtype, tuple(mu.shape), sigma.dtype, tuple(sigma.shape)))
+    return mu.detach().contiguous(), sigma.detach().contiguous()
+
+
+def gmm_bins(csr, pseudo, mu, sigma, x, row_scale=None, out=None):
+    """Z[r, k*Cin + c] = scale[r] * sum over the slots of r of w_k(pseudo[eid[slot]]) *
+    x[col[slot], c] (mp_gmm_aggregate_bins_f32); pseudo [E, D] in edge order, mu /
+    sigma [K, D].  out: a [n_rows, >= K*Cin] tensor to write into.  No autograd."""
+    nat = _lib.native()
+    pseudo, x = _nnconv_rows(pseudo, "pseudo"), _nnconv_rows(x, "x")
+    mu, sigma = _gmm_table(mu, sigma)
+    (K, D), c_in = mu.shape, x.shape[1]
+    if pseudo.shape[1] != D:
+        raise ValueError("mi355_mp: pseudo has %d columns, mu %d" % (pseudo.shape[1], D))
+    if out is None:
+        out = torch.empty((csr.n_rows, K * c_in), dtype=torch.float32, device=x.device)
+    if csr.n_rows:
+        _count_call(nat, "mp_gmm_aggregate_bins_f32", csr.struct("other"), pseudo.data_ptr(), pseudo.shape[0],
+                    pseudo.stride(0), D, mu.data_ptr(), sigma.data_ptr(), K, x.data_ptr(), x.stride(0), c_in,
+                    _lib.ptr(row_scale), out.data_ptr(), out.stride(0), _lib.stream_ptr(x.device))
+    return out
+
+
+def gmm_gather(csr, pseudo, mu, sigma, y, F, row_scale=None, bias=None, out=None):
+    """out[r, f] = scale[r] * sum over the slots of r and k < K (k ascending) of
+    w_k(pseudo[eid[slot]]) * y[col[slot], k*F + f] (+ bias) (mp_gmm_aggregate_gather_f32);
+    y [n_cols, K*F].  No autograd."""
+    nat = _lib.native()
+    pseudo, y = _nnconv_rows(pseudo, "pseudo"), _nnconv_rows(y, "y")
+    mu, sigma = _gmm_table(mu, sigma)
+    (K, D), F = mu.shape, int(F)
+    if pseudo.shape[1] != D:
+        raise ValueError("mi355_mp: pseudo has %d columns, mu %d" % (pseudo.shape[1], D))
+    if out is None:
+        out = torch.empty((csr.n_rows, F), dtype=torch.float32, device=y.device)
+    if csr.n_rows:
+        _count_call(nat, "mp_gmm_aggregate_gather_f32", csr.struct("other"), pseudo.data_ptr(), pseudo.shape[0],
+                    pseudo.stride(0), D, mu.data_ptr(), sigma.data_ptr(), K, y.data_ptr(), y.stride(0), F,
+                    _lib.ptr(row_scale), _lib.ptr(bias), out.data_ptr(), out.stride(0), _lib.stream_ptr(y.device))
+    return out
+
+
+def gmm_param_grad(rows, cols, pseudo, mu, sigma, dz, x, want_pseudo=False, dmu=None, dsigma=None, dpseudo=None):
+    """(dmu, dsigma, dpseudo or None) of mp_gmm_param_grad_f32: with dw[e, k] = sum_c
+    dz[rows[e], k*Cin + c] * x[cols[e], c] and t = dw * w_k(pseudo[e]), dmu[k, d] =
+    sum_e t (p_d - mu_kd) iv_kd, dsigma[k, d] = sum_e t ((p_d - mu_kd)^2 iv_kd)
+    (sigma_kd iv_kd), dpseudo[e, d] = -sum_k t (p_d - mu_kd) iv_kd.  Chunk partials
+    in a fixed order, then the chunks in order: bitwise reproducible.  rows / cols
+    int64 [E], range-checked by the caller (a CSR built from them has done it);
+    dpseudo is computed only with want_pseudo (or a dpseudo= tensor to write
+    into).  No autograd."""
+    nat = _lib.native()
+    pseudo, dz, x = _nnconv_rows(pseudo, "pseudo"), _nnconv_rows(dz, "dz"), _nnconv_rows(x, "x")
+    mu, sigma = _gmm_table(mu, sigma)
+    rows, cols = rows.contiguous(), cols.contiguous()
+    (K, D), E = mu.shape, rows.numel()
+    if cols.numel() != E or pseudo.shape[0] != E or pseudo.shape[1] != D:
+        raise ValueError("mi355_mp: rows / cols / pseudo must hold %d edges and pseudo %d columns (got %d, %s)"
+                         % (E, D, cols.numel(), tuple(pseudo.shape)))
+    for t, what in ((dmu, "dmu"), (dsigma, "dsigma")):
+        if t is not None and not (t.dtype == torch.float32 and tuple(t.shape) == (K, D) and t.is_contiguous()):
+            raise ValueError("mi355_mp: %s must be a contiguous float32 [%d, %d] tensor" % (what, K, D))
+    dmu = torch.empty((K, D), dtype=torch.float32, device=x.device) if dmu is None else dmu
+    dsigma = torch.empty((K, D), dtype=torch.float32, device=x.device) if dsigma is None else dsigma
+    if dpseudo is None and want_pseudo:
+        dpseudo = torch.empty((E, D), dtype=torch.float32, device=x.device)
+    if dpseudo is not None and not (dpseudo.dtype == torch.float32 and dpseudo.dim() == 2
+                                    and tuple(dpseudo.shape) == (E, D) and dpseudo.stride(1) in (0, 1)
+                                    and dpseudo.stride(0) >= D):
+        raise ValueError("mi355_mp: dpseudo must be a float32 [%d, %d] tensor with unit column stride" % (E, D))
+    ws_bytes = nat.mp_gmm_param_grad_workspace(E, K, D)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    _count_call(nat, "mp_gmm_param_grad_f32", rows.data_ptr(), cols.data_ptr(), E, pseudo.data_ptr(), pseudo.stride(0),
+                D, mu.data_ptr(), sigma.data_ptr(), K, dz.data_ptr(), dz.stride(0), x.data_ptr(), x.stride(0),
+                x.shape[1], dmu.data_ptr(), dsigma.data_ptr(), _lib.ptr(dpseudo),
+                0 if dpseudo is None else dpseudo.stride(0), ws.data_ptr(), ws_bytes, _lib.stream_ptr(x.device))
+    return dmu, dsigma, dpseudo
+
+
+def gmm_form(K, D, c_in, c_out, E, N):
+    """The forward's form, by the floats each form moves (a pure function of the shape):
+      bins    reads D + Cin floats per edge, writes Z [N, K Cin] and reads it back
+              in the GEMM:                 E (D + Cin)        + 2 N K Cin
+      gather  writes Y [N, K Cout] in the GEMM and gathers D + K Cout floats per
+              edge:                        E (D + K Cout)     +   N K Cout
+    The lower count wins, ties to bins (it keeps Z for g's gradient, the gather
+    form recomputes it in the backward)."""
+    bins = E * (D + c_in) + 2 * N * K * c_in
+    gather = E * (D + K * c_out) + N * K * c_out
+    return "bins" if bins <= gather else "gather"
+
+
+def _gmm_mix_matrix(g, K, c_in, c_out):
+    """G' [K Cin, Cout]: G'[k*Cin + c, m] = g[c, k*Cout + m] -- one permuting copy."""
+    return g.detach().view(c_in, K, c_out).permute(1, 0, 2).reshape(K * c_in, c_out)
+
+
+class _GMMPropagate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, pseudo, mu, sigma, g, bias, graph, reduce, form):
+        (K, D), c_in = mu.shape, x.shape[1]
+        c_out = g.shape[1] // K
+        csr = graph.dst
+        scale = None
+        if reduce == "mean":
+            scale = (1.0 / csr.degree().clamp(min=1).to(torch.float32)).contiguous()
+        Z = None
+        if form == "bins":
+            Gp = _gmm_mix_matrix(g, K, c_in, c_out)
+            Z = gmm_bins(csr, pseudo, mu, sigma, x, scale)
+            out = torch.mm(Z, Gp) if bias is None else torch.addmm(bias, Z, Gp)
+        else:
+            Y = torch.mm(x, g)                           # [N, K, Cout]: g's own column order
+            out = gmm_gather(csr, pseudo, mu, sigma, Y, c_out, scale, bias)
+        ctx.graph, ctx.has_bias = graph, bias is not None
+        # the cached Graph holds its edge_index weakly and builds the transposed CSR
+        # on first use, in backward: keep the tensor alive until then
+        ctx.save_for_backward(x, pseudo, mu, sigma, g, scale, Z if ctx.needs_input_grad[4] else None,
+                              graph._edge_index())
+        return out
+
+    @staticmethod
+    def backward(ctx, go):
+        x, pseudo, mu, sigma, g, scale, Z, edge_index = ctx.saved_tensors
+        graph = ctx.graph
+        (K, D), c_in = mu.shape, x.shape[1]
+        c_out = g.shape[1] // K
+        go = go.contiguous()
+        gx = gp = gmu = gsigma = gg = gb = None
+        if ctx.has_bias and ctx.needs_input_grad[5]:
+            gb = col_sums(go)
+        if ctx.needs_input_grad[4]:
+            if Z is None:                                # the gather form never built it
+                Z = gmm_bins(graph.dst, pseudo, mu, sigma, x, scale)
+            gGp = torch.mm(Z.t(), go)                    # Z carries the row scale
+            gg = gGp.view(K, c_in, c_out).permute(1, 0, 2).reshape(c_in, K * c_out)
+        want_x = ctx.needs_input_grad[0]
+        want_p, want_mu, want_sigma = ctx.needs_input_grad[1:4]
+        if want_x or want_p or want_mu or want_sigma:
+            gs = go if scale is None else go * scale.view(-1, 1)
+            dZ = torch.mm(gs, _gmm_mix_matrix(g, K, c_in, c_out).t())
+            if want_x:
+                # the transposed pass: rows = source nodes, gathers destination rows of dZ
+                gx = gmm_gather(graph.src, pseudo, mu, sigma, dZ, c_in)
+            if want_p or want_mu or want_sigma:
+                gmu, gsigma, gp = gmm_param_grad(edge_index[graph.i], edge_index[graph.j], pseudo, mu, sigma, dZ, x,
+                                                 want_pseudo=want_p)
+                gmu = gmu if want_mu else None
+                gsigma = gsigma if want_sigma else None
+        return gx, gp, gmu, gsigma, gg, gb, None, None, None
+
+
+def gmm_propagate(graph, x, pseudo, mu, sigma, g, reduce, form=None, bias=None):
+    """out[i] = AGGR_{e = (j -> i)} sum_k w_k(pseudo[e]) * (x[j] @ g)[k*M : (k+1)*M] (+ bias),
+    w_k(p) = exp(sum_d -0.5 (p_d - mu_kd)^2 / (1e-15 + sigma_kd^2))
+
+    GMMConv's propagate with shared Gaussians: the weights are evaluated inside
+    one segmented pass, plus one node-level GEMM; no [E, K, M] or [E, K] array.
+    pseudo [E, D] in edge order, mu / sigma [K, D], g [Cin, K*M].  reduce 'add'
+    or 'mean' (mean divides by max(deg, 1)); form None picks by gmm_form, 'bins'
+    / 'gather' force one.  Deterministic, native forward and backward: d x by the
+    gather kernel over the transposed CSR, d g by Z^T g_out with Z saved by the
+    bins form and recomputed after the gather form, d mu / d sigma / d pseudo by
+    gmm_param_grad (skipped when none of the three needs a gradient)."""
+    if reduce == "max":
+        raise NotImplementedError("mi355_mp: gmm_propagate has no aggr='max' (add and mean only)")
+    if reduce not in ("add", "sum", "mean"):
+        raise ValueError("unknown reduce %r" % (reduce,))
+    if form not in (None, "bins", "gather"):
+        raise ValueError("unknown form %r" % (form,))
+    _lib.require_device(x, pseudo, mu, sigma, g, bias)
+    # x also feeds a GEMM (x g of the gather form), whose rounding follows the operand layout: one layout
+    x, pseudo = _f32_2d(x, "x").contiguous(), _nnconv_rows(pseudo, "pseudo")
+    if mu.dtype != torch.float32 or sigma.dtype != torch.float32 or mu.dim() != 2 or mu.shape != sigma.shape:
+        raise ValueError("mi355_mp: mu and sigma must be float32 [K, D] (got %s %s, %s %s)"
+                         % (mu.dtype, tuple(mu.shape), sigma.dtype, tuple(sigma.shape)))
+    (K, D), c_in = mu.shape, x.shape[1]
+    if pseudo.shape[1] != D:
+        raise ValueError("mi355_mp: pseudo has %d columns, mu %d" % (pseudo.shape[1], D))
+    if g.dtype != torch.float32 or g.dim() != 2 or g.shape[0] != c_in or K == 0 or g.shape[1] % max(K, 1):
+        raise ValueError("mi355_mp: g must be float32 [%d, %d * Cout] (got %s %s)"
+                         % (c_in, K, g.dtype, tuple(g.shape)))
+    c_out = g.shape[1] // K
+    if bias is not None and tuple(bias.shape) != (c_out,):
+        raise ValueError("mi355_mp: bias must be [%d] (got %s)" % (c_out, tuple(bias.shape)))
+    if not gmm_ok(K, D, c_in, c_out):
+        raise NotImplementedError("mi355_mp: outside the fused GMMConv path's limits: "
+                                  + _lib.native().mp_last_error().decode(errors="replace"))
+    if pseudo.shape[0] != graph.dst.n_edges:
+        raise ValueError("mi355_mp: pseudo has %d rows, the graph %d edges" % (pseudo.shape[0], graph.dst.n_edges))
+    if x.shape[0] != graph.n_src:
+        raise ValueError("mi355_mp: x has %d rows, the graph %d source nodes" % (x.shape[0], graph.n_src))
+    if form is None:
+        form = gmm_form(K, D, c_in, c_out, pseudo.shape[0], x.shape[0])
+    reduce = "add" if reduce == "sum" else reduce
+    return _GMMPropagate.apply(x, pseudo, mu, sigma, g.contiguous(), bias, graph, reduce, form)
+
+
+# ---------------------------------------------------------------------------
 # RGCNConv: relational aggregation over a basis decomposition (csrc/mp_rgcn.hip)
 # ---------------------------------------------------------------------------
 

@@ -13,6 +13,7 @@ from .nn_conv import NNConv
 from .rgcn_conv import RGCNConv
 from .dna_conv import DNAConv
 from .edge_conv import EdgeConv, DynamicEdgeConv
+from .gmm_conv import GMMConv
 
 __all__ = ["MessagePassing", "GCNConv", "GATConv", "SAGEConv", "GraphConv", "ChebConv", "AGNNConv", "SGConv", "GINConv",
-           "SplineConv", "PointConv", "NNConv", "RGCNConv", "DNAConv", "EdgeConv", "DynamicEdgeConv"]
+           "SplineConv", "PointConv", "NNConv", "RGCNConv", "DNAConv", "EdgeConv", "DynamicEdgeConv", "GMMConv"]
