@@ -796,6 +796,53 @@ int64_t mp_gmm_param_grad_f32(const int64_t* rows, const int64_t* cols, int64_t 
                               int64_t lddz, const float* x, int64_t ldx, int32_t Cin, float* dmu, float* dsigma,
                               float* dpseudo, int64_t lddp, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- ARMAConv: K stacks, one fused launch per recurrent step (csrc/mp_arma.hip)
+ * PyG 1.4.3's nn.conv.ARMAConv [U]: step t of T, per stack k,
+ *   H_{t+1}[k] = act(A (H_t[k] W_t[k]) + x_drop V_t[k] + b_t[k]),   out = mean_k H_T[k]
+ * with A = D^-1/2 W D^-1/2 summed at edge_index[0].  Every node-level operand
+ * is [rows, K * C] fp32, STACK-MINOR: entry (k, c) of a row at k * C + c, the row
+ * P = mp_arma_width(K, C) = K * C rounded up to 4 floats wide, its ld a multiple
+ * of 4 and its base 16-byte aligned; the P - K * C padding columns of every
+ * output are written as zeros, those of the inputs are never used.  lap
+ * [n_edges] holds the edge coefficients in the SLOT order of g.  Limits
+ * (mp_arma_ok != 0; needs no GPU): K, C >= 1, C <= 64, K * C <= 256 and
+ * K * C * C <= 8192 (the weight block a workgroup stages in LDS: 32 KiB) -- every
+ * K * C <= 256 with C <= 32, and C = 64 with K <= 2.
+ *   mp_arma_step_f32 (g keyed on edge_index[0], gathering y [g->n_cols, ldy] at
+ *   edge_index[1]): per row n, acc = sum_{slots of n} lap[slot] * y[col[slot], :]
+ *   (slot order, hub rows split over tasks and combined in task order), then once
+ *   per complete row h = acc + s[n, :] (s: the skip term with the bias folded in),
+ *   h = max(h, 0) when relu = 1, and
+ *     h_out[n, :] = h                                  when h_out != NULL
+ *     y_next[n, k, :] = h[k, :] w_next[k]              with w_next [K, C, C] (a next step exists)
+ *     out[n, c] = (1 / K) sum_k h[k, c]  (k ascending) on the last step, out [n_rows, ldo >= C]
+ *   exactly one of (w_next, y_next) and out is given.  A row without slots gets act(s).
+ *   mp_arma_step_bwd_f32 (g keyed on edge_index[1], gathering dpre [g->n_cols,
+ *   ldp] at edge_index[0], lap in that CSR's slot order):
+ *     dy[n, :] = sum_{slots of n} lap[slot] * dpre[col[slot], :]
+ *     dpre_prev[n, k, :] = (dy[n, k, :] w_t[k]) * (h[n, k, :] > 0)
+ *   w_t [K, C, C] holds each stack's W_t TRANSPOSED; h = NULL drops the mask
+ *   (identity activation); w_t = dpre_prev = NULL stores dy alone (step 0).
+ * ws: mp_arma_workspace(g, K, C) bytes (the partial slabs of split rows).  Every
+ * array is passed with its extent in bytes and checked before any launch.  fp32,
+ * fixed summation order, no atomics: two calls give the same bits.  Additions to
+ * ABI 7 that return int64_t like the GMMConv calls: the launches enqueued, >= 0,
+ * or -(MP_ERR_* code) with the reason in mp_last_error(); mp_arma_width answers a
+ * question (or -MP_ERR_ARG outside the limits). */
+int64_t mp_arma_ok(int32_t K, int32_t C);
+int64_t mp_arma_width(int32_t K, int32_t C);
+size_t mp_arma_workspace(const mp_csr* g, int32_t K, int32_t C);
+int64_t mp_arma_step_f32(const mp_csr* g, const float* lap, size_t lap_bytes, const float* y, int64_t ldy,
+                         size_t y_bytes, const float* s, int64_t lds, size_t s_bytes, const float* w_next,
+                         size_t w_bytes, int32_t K, int32_t C, int32_t relu, float* h_out, int64_t ldh,
+                         size_t h_bytes, float* y_next, int64_t ldn, size_t n_bytes, float* out, int64_t ldo,
+                         size_t out_bytes, void* ws, size_t ws_bytes, void* stream);
+int64_t mp_arma_step_bwd_f32(const mp_csr* g, const float* lap, size_t lap_bytes, const float* dpre, int64_t ldp,
+                             size_t dpre_bytes, const float* w_t, size_t w_bytes, const float* h, int64_t ldh,
+                             size_t h_bytes, int32_t K, int32_t C, float* dy, int64_t ldd, size_t dy_bytes,
+                             float* dpre_prev, int64_t ldq, size_t q_bytes, void* ws, size_t ws_bytes,
+                             void* stream);
+
 /* ---- Attention readout: Set2Set / GlobalAttention (csrc/mp_glob.hip) ---------
  * PyG 1.4.3's nn.glob.Set2Set and nn.glob.GlobalAttention [U] share one step: a
  * softmax of one scalar per node over each graph, then the softmax-weighted sum

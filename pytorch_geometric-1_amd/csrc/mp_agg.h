@@ -504,6 +504,10 @@ __device__ __forceinline__ void run_slots(Red& red, const AggArgs& p,
   }
 }
 
+// NOTE: mp_arma.hip carries a copy of this kernel's task walk and of k_agg_fixup's chain merge
+// (k_arma_main, k_arma_fixup: the same code behind a workgroup-wide LDS staging step, one feature
+// tile, a second argument block).  A change to the walk, the slab slots or the merge order here
+// must be mirrored there.
 template <class Red, int VEC, int U, int L>
 __global__ __launch_bounds__(kBlock) void k_agg_main(AggArgs p) {
   using GR = Grp<L>;

@@ -231,6 +231,14 @@ SIGNATURES = {
     "mp_gmm_param_grad_workspace": (sz, [i64, i32, i32]),
     "mp_gmm_param_grad_f32": (i64, [c_p, c_p, i64, c_p, i64, i32, c_p, c_p, i32, c_p, i64, c_p, i64, i32, c_p, c_p,
                                     c_p, i64, c_p, sz, c_p]),
+    # ARMAConv (csrc/mp_arma.hip): int64 returns like GMMConv's, the sign tested by ops._count_call
+    "mp_arma_ok": (i64, [i32, i32]),               # an answer (0 or 1), not a status
+    "mp_arma_width": (i64, [i32, i32]),            # floats of one stacked row, or -MP_ERR_ARG
+    "mp_arma_workspace": (sz, [ctypes.POINTER(MpCsr), i32, i32]),
+    "mp_arma_step_f32": (i64, [ctypes.POINTER(MpCsr), c_p, sz, c_p, i64, sz, c_p, i64, sz, c_p, sz, i32, i32, i32,
+                               c_p, i64, sz, c_p, i64, sz, c_p, i64, sz, c_p, sz, c_p]),
+    "mp_arma_step_bwd_f32": (i64, [ctypes.POINTER(MpCsr), c_p, sz, c_p, i64, sz, c_p, sz, c_p, i64, sz, i32, i32,
+                                   c_p, i64, sz, c_p, i64, sz, c_p, sz, c_p]),
     # the attention readout (csrc/mp_glob.hip): int64 returns again, the sign tested by ops._count_call
     "mp_readout_path": (i64, [i64, i32]),          # an answer (0, 1 or 2), or -MP_ERR_ARG
     "mp_readout_chunk": (i64, [i32]),              # nodes per chunk of a split graph, or -MP_ERR_ARG

@@ -2401,6 +2401,274 @@ def dna_propagate(graph, q, k, v, norm, heads, p=0.0, seed=None):
 
 
 # ---------------------------------------------------------------------------
+# ARMAConv: K stacks, one fused launch per recurrent step (csrc/mp_arma.hip)
+# ---------------------------------------------------------------------------
+
+def arma_ok(K, C):
+    """Whether (K stacks, C channels) lies inside the fused step's limits (mp_arma_ok; needs no GPU)."""
+    return bool(_lib.native().mp_arma_ok(int(K), int(C)))
+
+
+def arma_width(K, C):
+    """Floats of one stacked row: K * C rounded up to 4 (mp_arma_width; needs no GPU)."""
+    P = int(_lib.native().mp_arma_width(int(K), int(C)))
+    if P < 0:
+        raise ValueError("mi355_mp: " + _lib.native().mp_last_error().decode(errors="replace"))
+    return P
+
+
+def _arma_rows(t, P, what):
+    t = _nnconv_rows(t, what)
+    if t.shape[1] != P:
+        raise ValueError("mi355_mp: %s must be [rows, %d] (the stacked row), got %s" % (what, P, tuple(t.shape)))
+    if t.stride(0) % 4 or t.data_ptr() % 16:
+        t = t.contiguous()
+    return t
+
+
+def _arma_out(out, rows, width, dev):
+    return torch.empty((rows, width), dtype=torch.float32, device=dev) if out is None else out
+
+
+def _arma_mat(t):
+    return (_lib.ptr(t), t.stride(0) if t is not None else 0, _extent_bytes(t) if t is not None else 0)
+
+
+def _arma_ws(nat, g, K, C, dev):
+    n = nat.mp_arma_workspace(g, K, C)
+    return torch.empty(n, dtype=torch.uint8, device=dev), n
+
+
+def arma_step(csr, lap_csr, y, s, K, C, relu=True, w_next=None, want_hidden=False, out=None, hidden=None):
+    """One recurrent step over the stacked layout (mp_arma_step_f32): per row n of csr
+    (keyed on edge_index[0]) h = act(sum over its slots of lap_csr[slot] * y[col[slot]] +
+    s[n]).  With w_next [K, C, C] the result is the next step's operand, out[n, k] =
+    h[k] @ w_next[k] ([n_rows, P]); without it the layer's output, the mean of h over
+    the stacks ([n_rows, C]).  want_hidden / hidden=: h itself is stored too.  Returns
+    (out, hidden or None).  No autograd."""
+    nat = _lib.native()
+    K, C = int(K), int(C)
+    P = arma_width(K, C)
+    y, s = _arma_rows(y, P, "y"), _arma_rows(s, P, "s")
+    dev = y.device
+    out = _arma_out(out, csr.n_rows, P if w_next is not None else C, dev)
+    if want_hidden or hidden is not None:
+        hidden = _arma_out(hidden, csr.n_rows, P, dev)
+    if w_next is not None:
+        w_next = w_next.detach().to(torch.float32).contiguous()
+    if csr.n_rows:
+        g = csr.struct("other")
+        ws, ws_bytes = _arma_ws(nat, g, K, C, dev)
+        nxt, last = (out, None) if w_next is not None else (None, out)
+        _count_call(nat, "mp_arma_step_f32", g, lap_csr.data_ptr(), _lib.nbytes(lap_csr), *_arma_mat(y), *_arma_mat(s),
+                    _lib.ptr(w_next), _lib.nbytes(w_next), K, C, 1 if relu else 0, *_arma_mat(hidden), *_arma_mat(nxt),
+                    *_arma_mat(last), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
+    return out, hidden
+
+
+def arma_step_backward(csr, lap_csr, dpre, K, C, w_t=None, h=None, dy=None, out=None):
+    """The step's backward over the transposed CSR (keyed on edge_index[1], lap_csr in
+    its slot order; mp_arma_step_bwd_f32): dy[n] = sum over the slots of lap * dpre[col],
+    and with w_t [K, C, C] (each stack's W_t transposed) the previous step's
+    dpre_prev[n, k] = (dy[n, k] @ w_t[k]) * (h[n, k] > 0) (h None: no mask).  Returns
+    (dy, dpre_prev or None).  No autograd."""
+    nat = _lib.native()
+    K, C = int(K), int(C)
+    P = arma_width(K, C)
+    dpre = _arma_rows(dpre, P, "dpre")
+    dev = dpre.device
+    dy = _arma_out(dy, csr.n_rows, P, dev)
+    if w_t is not None:
+        w_t = w_t.detach().to(torch.float32).contiguous()
+        out = _arma_out(out, csr.n_rows, P, dev)
+        if h is not None:
+            h = _arma_rows(h, P, "h")
+    if csr.n_rows:
+        g = csr.struct("other")
+        ws, ws_bytes = _arma_ws(nat, g, K, C, dev)
+        _count_call(nat, "mp_arma_step_bwd_f32", g, lap_csr.data_ptr(), _lib.nbytes(lap_csr), *_arma_mat(dpre),
+                    _lib.ptr(w_t), _lib.nbytes(w_t), *_arma_mat(h if w_t is not None else None), K, C, *_arma_mat(dy),
+                    *_arma_mat(out if w_t is not None else None), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
+    return dy, (out if w_t is not None else None)
+
+
+def _arma_stack_in(w, P):
+    """[K, F, C] -> [F, P]: one GEMM operand over the stacked layout, padding columns zero."""
+    K, F, C = w.shape
+    m = w.permute(1, 0, 2).reshape(F, K * C)
+    return torch.nn.functional.pad(m, (0, P - K * C)) if P != K * C else m
+
+
+def _arma_tn(a, b, rows=2048):
+    """a^T b for tall contiguous a [N, F], b [N, P] (a parameter gradient: the sum runs over the
+    nodes).  One GEMM with an F x P output and N as its inner dimension runs on a handful of
+    workgroups (322 us at N = 100,000, F = 64, P = 48); the same sum as one batched GEMM over
+    chunks of `rows` nodes plus the chunks' sum in chunk order fills the GPU and stays deterministic."""
+    n = a.shape[0]
+    s = n // rows
+    if s < 16:
+        return torch.mm(a.t(), b)
+    m = s * rows
+    out = torch.bmm(a[:m].view(s, rows, -1).transpose(1, 2), b[:m].view(s, rows, -1)).sum(0)
+    return out if m == n else out.addmm_(a[m:].t(), b[m:])
+
+
+def _arma_unstack(m, K, C):
+    """[F, P] -> [K, F, C]"""
+    return m[:, :K * C].reshape(m.shape[0], K, C).permute(1, 0, 2)
+
+
+class _ARMAPropagate(torch.autograd.Function):
+    """inputs after the fixed ones: x, then ws, vs, bias (n_b of them, 0 or len(vs)), then the
+    T dropped copies of x (none without dropout: every step reads x itself)."""
+
+    @staticmethod
+    def forward(ctx, graph, lap, edge_index, K, C, T, shared, relu, want_hidden, n_w, n_v, n_b, x, *rest):
+        ws, vs, bias, xds = rest[:n_w], rest[n_w:n_w + n_v], rest[n_w + n_v:n_w + n_v + n_b], rest[n_w + n_v + n_b:]
+        P, KC = arma_width(K, C), K * C
+        wi = (lambda t: min(t, 1)) if shared else (lambda t: t)
+        vi = (lambda t: 0) if shared else (lambda t: t)
+        dst = graph.dst
+        lap_dst = in_csr_order(dst, lap)
+        Vp = [_arma_stack_in(v, P) for v in vs]
+        bp = [torch.nn.functional.pad(b.reshape(KC), (0, P - KC)) for b in bias]
+        W0p = _arma_stack_in(ws[0], P)
+        S = None
+        if not xds and shared:
+            # one GEMM for Y_0 and the S every step reuses; Y and S are then column slices of YS with row
+            # stride 2P (a multiple of 4 floats, 16-byte aligned bases: what the step asks of an operand)
+            YS = torch.mm(x, torch.cat([W0p, Vp[0]], dim=1))
+            Y, S = YS[:, :P], YS[:, P:]
+            if bp:
+                S += bp[0]
+        else:
+            Y = torch.mm(x, W0p)
+        keep = want_hidden or any(ctx.needs_input_grad)
+        Hs, out = [], None
+        for t in range(T):
+            if xds or not shared:
+                xd = xds[t] if xds else x
+                S = torch.addmm(bp[vi(t)], xd, Vp[vi(t)]) if bp else torch.mm(xd, Vp[vi(t)])
+            last = t == T - 1
+            nxt, h = arma_step(dst, lap_dst, Y, S, K, C, relu, None if last else ws[wi(t + 1)], want_hidden=keep)
+            if keep:
+                Hs.append(h)
+            Y, out = (None, nxt) if last else (nxt, None)
+        ctx.graph, ctx.cfg = graph, (K, C, T, shared, relu, n_w, n_v, n_b, len(xds))
+        # edge_index: the cached graph holds it weakly, and the backward builds the transposed CSR from it
+        ctx.save_for_backward(lap, x, edge_index, *rest, *Hs)
+        if want_hidden:
+            ctx.mark_non_differentiable(*Hs)
+            return (out, *Hs)
+        return out
+
+    @staticmethod
+    def backward(ctx, g_out, *_g_hidden):
+        K, C, T, shared, relu, n_w, n_v, n_b, n_x = ctx.cfg
+        lap, x = ctx.saved_tensors[:2]
+        rest = ctx.saved_tensors[3:]
+        ws, vs = rest[:n_w], rest[n_w:n_w + n_v]
+        xds = rest[n_w + n_v + n_b:n_w + n_v + n_b + n_x]
+        Hs = rest[n_w + n_v + n_b + n_x:]
+        P, KC = arma_width(K, C), K * C
+        wi = (lambda t: min(t, 1)) if shared else (lambda t: t)
+        vi = (lambda t: 0) if shared else (lambda t: t)
+        src = ctx.graph.src                     # keyed on edge_index[1], gathers at edge_index[0]
+        lap_src = in_csr_order(src, lap)
+        pad = torch.nn.functional.pad
+        need = ctx.needs_input_grad
+        need_x, base = need[12], 13
+        need_w, need_v = need[base:base + n_w], need[base + n_w:base + n_w + n_v]
+        need_b = need[base + n_w + n_v:base + n_w + n_v + n_b]
+        need_xd = need[base + n_w + n_v + n_b:]
+        dW, dV, dB = [None] * n_w, [None] * n_v, [None] * n_b
+        dXd = [None] * n_x
+        dx = None
+
+        def add(lst, i, v):
+            lst[i] = v if lst[i] is None else lst[i] + v
+
+        dpre = pad((g_out * (1.0 / K)).repeat(1, K), (0, P - KC))
+        if relu:
+            dpre = dpre * (Hs[T - 1] > 0)
+        for t in range(T - 1, -1, -1):
+            dpre = dpre.contiguous()
+            xd = xds[t] if n_x else x
+            if need_v[vi(t)]:
+                add(dV, vi(t), _arma_unstack(_arma_tn(xd, dpre), K, C))
+            if n_b and need_b[vi(t)]:
+                add(dB, vi(t), col_sums(dpre)[:KC].reshape(K, 1, C))
+            if (n_x and need_xd[t]) or (not n_x and need_x):
+                Vp = _arma_stack_in(vs[vi(t)], P)
+                if n_x:
+                    dXd[t] = torch.mm(dpre, Vp.t())
+                else:
+                    dx = torch.mm(dpre, Vp.t()) if dx is None else torch.addmm(dx, dpre, Vp.t())
+            if t > 0:
+                w = ws[wi(t)]
+                dy, prev = arma_step_backward(src, lap_src, dpre, K, C, w.transpose(1, 2), Hs[t - 1] if relu else None)
+                if need_w[wi(t)]:
+                    h = Hs[t - 1][:, :KC].reshape(-1, K, C)
+                    add(dW, wi(t), torch.bmm(h.permute(1, 2, 0), dy[:, :KC].reshape(-1, K, C).permute(1, 0, 2)))
+                dpre = prev
+            elif need_w[0] or need_x:
+                dy, _ = arma_step_backward(src, lap_src, dpre, K, C)
+                if need_w[0]:
+                    add(dW, 0, _arma_unstack(_arma_tn(x, dy), K, C))
+                if need_x:
+                    W0p = _arma_stack_in(ws[0], P)
+                    dx = torch.mm(dy, W0p.t()) if dx is None else torch.addmm(dx, dy, W0p.t())
+        return (None,) * 12 + (dx, *dW, *dV, *dB, *dXd)
+
+
+def arma_laplacian(graph, edge_weight=None):
+    """lap[e] = dinv[row] * w[e] * dinv[col], deg = scatter_add(w, row), dinv = deg^-1/2 with
+    inf -> 0, by the native degree and norm ops; graph keyed on row = edge_index[0], w None =
+    ones.  fp32 [E] in edge order, no autograd."""
+    ei, n = graph._edge_index(), graph.n_dst
+    if edge_weight is None:
+        return gcn_norm_weights(ei, n)
+    check_row_index(ei, n, "arma_laplacian")
+    w = edge_weight.detach().to(torch.float32).contiguous()
+    return norm_from_degree(ei[0], ei[1], segment_sum_serial(graph.dst, w), w, trusted=True)
+
+
+def arma_propagate(graph, x, ws, vs, bias, K, C, T, shared, relu, p, training, want_hidden=False, edge_weight=None,
+                   lap=None):
+    """ARMAConv's T recurrent steps over K stacks, one fused launch each
+    (mp_arma_step_f32; csrc/mp_arma.hip), forward and backward.
+
+    graph: keyed on edge_index[0] as the destination (flow "target_to_source");
+    edge_weight [E] or None (ones), or lap: their symmetric normalisation already
+    computed (arma_laplacian; no gradient either way).  ws / vs / bias: the layer's parameter lists ([K, ., C], [K, F, C],
+    [K, 1, C] or None).  relu: ReLU or identity.  p / training: F.dropout(x, p,
+    training) on the skip input, called once per step in step order, so the same
+    torch seed draws the masks the unfused recipe draws.  Y_0 = x ws[0] and the skip
+    terms are single GEMMs into the stacked [N, K*C] layout; with shared weights
+    and no dropout one GEMM over [F, 2 K C] gives Y_0 and the S every step reuses.
+    Returns out [N, C], or (out, [H_1 .. H_T]) with want_hidden (each [N, P] stacked,
+    P = arma_width(K, C); the state the backward keeps anyway)."""
+    _lib.require_device(x, edge_weight, lap, *ws, *vs)
+    K, C, T = int(K), int(C), int(T)
+    if not arma_ok(K, C):
+        raise NotImplementedError("mi355_mp: outside the fused ARMA step's limits: K = %d, C = %d" % (K, C))
+    x = _f32_2d(x, "x").contiguous()
+    if x.shape[0] != graph.n_dst or x.shape[0] != graph.n_src:
+        raise ValueError("mi355_mp: %d nodes, the graph %d sources and %d destinations"
+                         % (x.shape[0], graph.n_src, graph.n_dst))
+    if (edge_weight is not None and edge_weight.requires_grad) or (lap is not None and lap.requires_grad):
+        raise NotImplementedError("mi355_mp: arma_propagate has no gradient with respect to the edge weights")
+    if lap is None:
+        lap = arma_laplacian(graph, edge_weight)
+    bias = list(bias) if bias is not None else []
+    drop = bool(training) and float(p) > 0.0
+    xds = [torch.nn.functional.dropout(x, p=float(p), training=True) for _ in range(T)] if drop else []
+    res = _ARMAPropagate.apply(graph, lap, graph._edge_index(), K, C, T, bool(shared), bool(relu), bool(want_hidden), len(ws), len(vs),
+                               len(bias), x, *ws, *vs, *bias, *xds)
+    return (res[0], list(res[1:])) if want_hidden else res
+
+
+# ---------------------------------------------------------------------------
 # TopKPooling (PyG 1.4.3 nn.pool.topk_pool [U]; csrc/mp_pool.hip)
 # ---------------------------------------------------------------------------
 

@@ -14,6 +14,8 @@ from .rgcn_conv import RGCNConv
 from .dna_conv import DNAConv
 from .edge_conv import EdgeConv, DynamicEdgeConv
 from .gmm_conv import GMMConv
+from .arma_conv import ARMAConv
 
 __all__ = ["MessagePassing", "GCNConv", "GATConv", "SAGEConv", "GraphConv", "ChebConv", "AGNNConv", "SGConv", "GINConv",
-           "SplineConv", "PointConv", "NNConv", "RGCNConv", "DNAConv", "EdgeConv", "DynamicEdgeConv", "GMMConv"]
+           "SplineConv", "PointConv", "NNConv", "RGCNConv", "DNAConv", "EdgeConv", "DynamicEdgeConv", "GMMConv",
+           "ARMAConv"]
