@@ -1069,6 +1069,61 @@ int64_t mp_dna_backward_src_f32(const mp_csr* g, const float* q, int64_t ldq, si
 int64_t mp_dna_dropout_keep(uint64_t seed, float p_drop, int32_t H, int32_t T, int64_t n_edges, uint8_t* keep,
                             size_t keep_bytes, void* stream);
 
+/* ---- AGNNConv: cosine attention in one gather pass, with backward (csrc/mp_agnn.hip)
+ * PyG 1.4.3 nn.conv.agnn_conv [U] on an edge list that already holds its self loops:
+ *   xn = x / max(|x|_2, 1e-12),  s_ij = beta <xn_i, xn_j>,
+ *   a_ij = exp(s_ij - m_i) / (sum_j exp(s_ij - m_i) + 1e-16),  out_i = sum_j a_ij x_j.
+ * The gathered row x_j gives the score and is the message; no [E, F] array exists.
+ * g is square (g->n_cols == g->n_rows: x serves both ends).  Rows: x, out, gout, u,
+ * dx [n_rows, ld >= F]; rn, lse [n_rows]; alpha, bds [ids] in edge-id order (ids =
+ * g->n_ids, or g->n_edges); beta, dbeta: DEVICE pointers to one float (the layer's
+ * parameter or buffer: no host read).  Every array travels with its extent in
+ * bytes, checked before any launch.  Limit (mp_agnn_ok != 0): 1 <= F <= 1024.
+ * A group of min(64, pow2 >= elements) lanes owns a unit and holds its row in
+ * registers, as dwordx4 elements where F % 4 == 0 and every operand is 16-byte
+ * aligned with ld % 4 == 0, as single floats otherwise; slots are walked in CSR
+ * order, fp32, deterministic, no atomics.  On a CSR whose schedule has g->chunk >=
+ * mp_agnn_split_chunk() (64) a unit is a task and a row cut by a task boundary is
+ * combined from slab partials by a fix-up launch in task order (as mp_dna_*: slot
+ * 2 * task a continuation, 2 * task + 1 a head); otherwise a unit walks its row.
+ * ws: mp_agnn_workspace(g, F, pass) bytes, always required; one layout
+ * (csrc/mp_agnn.hip AgnnWs).  Every entry of every output row is written once.
+ *   mp_agnn_rnorm_f32: rn[k] = 1 / max(|x_k|, 1e-12).
+ *   mp_agnn_aggregate_f32 (g: destination CSR): out, and lse = m + log(l + 1e-16).
+ *   mp_agnn_backward_dst_f32 (same CSR): q_i = <gout_i, out_i>; per slot c = <x_i, x_j>
+ *     rn_i rn_j, a = exp(beta c - lse_i), ds = a (<gout_i, x_j> - q_i); alpha[eid] = a,
+ *     bds[eid] = beta ds, u_i = sum bds rn_j x_j, *dbeta = sum ds c (rows summed in a
+ *     fixed order in two stages).
+ *   mp_agnn_backward_src_f32 (g: the source-keyed CSR): val_j = sum alpha_e gout_i,
+ *     w_j = sum bds_e rn_i x_i, t = u_j + w_j, dx_j = val_j + rn_j (t - xn_j <xn_j, t>).
+ * Additions to ABI 7 that return int64_t like the DNA calls: the launches enqueued,
+ * >= 0, or -(MP_ERR_* code) with the reason in mp_last_error() -- for a bad argument
+ * (-MP_ERR_ARG), before any launch.  mp_agnn_ok, mp_agnn_split_chunk and
+ * mp_agnn_workspace answer a question and need no GPU. */
+#define MP_AGNN_PASS_FWD 0
+#define MP_AGNN_PASS_DST 1
+#define MP_AGNN_PASS_SRC 2
+int64_t mp_agnn_ok(int32_t F);
+int64_t mp_agnn_split_chunk(void);
+size_t mp_agnn_workspace(const mp_csr* g, int32_t F, int32_t pass);
+int64_t mp_agnn_rnorm_f32(const float* x, int64_t ldx, size_t x_bytes, int64_t n, int32_t F, float* rn,
+                          size_t rn_bytes, void* stream);
+int64_t mp_agnn_aggregate_f32(const mp_csr* g, const float* x, int64_t ldx, size_t x_bytes, const float* rn,
+                              size_t rn_bytes, const float* beta, int32_t F, float* out, int64_t ldo,
+                              size_t out_bytes, float* lse, size_t lse_bytes, void* ws, size_t ws_bytes,
+                              void* stream);
+int64_t mp_agnn_backward_dst_f32(const mp_csr* g, const float* x, int64_t ldx, size_t x_bytes, const float* rn,
+                                 size_t rn_bytes, const float* beta, int32_t F, const float* out, int64_t ldo,
+                                 size_t out_bytes, const float* lse, size_t lse_bytes, const float* gout,
+                                 int64_t ldg, size_t g_bytes, float* alpha, size_t alpha_bytes, float* bds,
+                                 size_t bds_bytes, float* u, int64_t ldu, size_t u_bytes, float* dbeta, void* ws,
+                                 size_t ws_bytes, void* stream);
+int64_t mp_agnn_backward_src_f32(const mp_csr* g, const float* x, int64_t ldx, size_t x_bytes, const float* rn,
+                                 size_t rn_bytes, int32_t F, const float* gout, int64_t ldg, size_t g_bytes,
+                                 const float* alpha, size_t alpha_bytes, const float* bds, size_t bds_bytes,
+                                 const float* u, int64_t ldu, size_t u_bytes, float* dx, int64_t lddx,
+                                 size_t dx_bytes, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- TopKPooling: score, per-graph select, gate, filter_adj (csrc/mp_pool.hip)
  * PyG 1.4.3 nn.pool.topk_pool [U] as one deterministic native path: no atomics
  * on values (two integer counters and one integer maximum aside), no dense

@@ -291,7 +291,19 @@ SIGNATURES = {
     "mp_link_grad_rows_f32": (i64, [c_p, c_p, c_p, i64, i64, c_p, i64, c_p, i64, i64, i32, i32, c_p, i64, sz, c_p]),
     "mp_neg_sample": (i64, [c_p, sz, c_p, i64, i32, u64, i64, c_p, c_p, sz, c_p]),
     "mp_neg_sample_rows": (i64, [c_p, sz, c_p, i64, u64, c_p, i64, c_p, sz, c_p]),
+    # AGNNConv (csrc/mp_agnn.hip): int64 returns again, the sign tested by ops._count_call
+    "mp_agnn_ok": (i64, [i32]),                    # an answer (0 or 1), not a status
+    "mp_agnn_split_chunk": (i64, []),              # the schedule's task size from which the kernels walk tasks
+    "mp_agnn_workspace": (sz, [ctypes.POINTER(MpCsr), i32, i32]),
+    "mp_agnn_rnorm_f32": (i64, [c_p, i64, sz, i64, i32, c_p, sz, c_p]),
+    "mp_agnn_aggregate_f32": (i64, [ctypes.POINTER(MpCsr), c_p, i64, sz, c_p, sz, c_p, i32, c_p, i64, sz, c_p, sz,
+                                    c_p, sz, c_p]),
+    "mp_agnn_backward_dst_f32": (i64, [ctypes.POINTER(MpCsr), c_p, i64, sz, c_p, sz, c_p, i32, c_p, i64, sz, c_p, sz,
+                                       c_p, i64, sz, c_p, sz, c_p, sz, c_p, i64, sz, c_p, c_p, sz, c_p]),
+    "mp_agnn_backward_src_f32": (i64, [ctypes.POINTER(MpCsr), c_p, i64, sz, c_p, sz, i32, c_p, i64, sz, c_p, sz, c_p,
+                                       sz, c_p, i64, sz, c_p, i64, sz, c_p, sz, c_p]),
 }
+MP_AGNN_PASS_FWD, MP_AGNN_PASS_DST, MP_AGNN_PASS_SRC = 0, 1, 2
 MP_NEG_FULL = 0
 MP_NEG_UPPER = 1
 

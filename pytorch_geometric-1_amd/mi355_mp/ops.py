@@ -2401,6 +2401,162 @@ def dna_propagate(graph, q, k, v, norm, heads, p=0.0, seed=None):
 
 
 # ---------------------------------------------------------------------------
+# AGNNConv: cosine attention in one gather pass, with backward (csrc/mp_agnn.hip)
+# ---------------------------------------------------------------------------
+
+def agnn_ok(F):
+    """Whether rows of F features lie inside the fused path's limit (mp_agnn_ok)."""
+    return bool(_lib.native().mp_agnn_ok(int(F)))
+
+
+def agnn_split_chunk():
+    """The schedule task size from which the AGNN kernels walk tasks and split long
+    rows (mp_agnn_split_chunk; needs no GPU)."""
+    return int(_lib.native().mp_agnn_split_chunk())
+
+
+def agnn_target_tasks(n_rows, n_edges):
+    """graph_for's target_tasks for an AGNN layer: tasks of max(agnn_split_chunk(),
+    the default chunk) units, as dna_target_tasks."""
+    from .graph import auto_chunk
+    want = agnn_split_chunk()
+    if auto_chunk(n_rows, n_edges) >= want:
+        return None
+    return max((int(n_rows) + int(n_edges)) // want, 1)
+
+
+def _agnn_ws(nat, csr, F, which, dev):
+    n = nat.mp_agnn_workspace(csr.struct("other"), int(F), which)
+    ws = torch.empty(n, dtype=torch.uint8, device=dev)
+    return ws, ws.data_ptr(), n
+
+
+def _agnn_rows(t, what, n, F):
+    t = _nnconv_rows(t, what)
+    if tuple(t.shape) != (n, F):
+        raise ValueError("mi355_mp: %s must be [%d, %d] (got %s)" % (what, n, F, tuple(t.shape)))
+    return t
+
+
+def _agnn_beta(beta, dev):
+    if not (torch.is_tensor(beta) and beta.dtype == torch.float32 and beta.numel() == 1 and beta.device == dev):
+        raise TypeError("mi355_mp: beta must be one float32 on %s (read on the device, never on the host)" % (dev,))
+    return beta.detach().contiguous()
+
+
+def agnn_rnorm(x):
+    """rn[k] = 1 / max(|x_k|_2, 1e-12), fp32 [n] (mp_agnn_rnorm_f32).  No autograd."""
+    nat = _lib.native()
+    x = _nnconv_rows(x, "x")
+    rn = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+    _count_call(nat, "mp_agnn_rnorm_f32", x.data_ptr(), x.stride(0), _extent_bytes(x), x.shape[0], x.shape[1],
+                rn.data_ptr(), _lib.nbytes(rn), _lib.stream_ptr(x.device))
+    return rn
+
+
+def agnn_aggregate(csr, x, rn, beta):
+    """(out [n, F], lse [n]) over the destination CSR: out_i = sum over the slots (j ->
+    i) of softmax_j(beta cos(x_i, x_j)) x_j with the 1e-16 of utils.softmax, lse = m +
+    log(l + 1e-16) (mp_agnn_aggregate_f32).  rn = agnn_rnorm(x).  No autograd."""
+    nat = _lib.native()
+    x = _nnconv_rows(x, "x")
+    n, F = x.shape
+    dev = x.device
+    beta = _agnn_beta(beta, dev)
+    out = torch.empty((n, F), dtype=torch.float32, device=dev)
+    lse = torch.empty(n, dtype=torch.float32, device=dev)
+    ws, ws_ptr, ws_bytes = _agnn_ws(nat, csr, F, _lib.MP_AGNN_PASS_FWD, dev)
+    _count_call(nat, "mp_agnn_aggregate_f32", csr.struct("other"), x.data_ptr(), x.stride(0), _extent_bytes(x),
+                rn.data_ptr(), _lib.nbytes(rn), beta.data_ptr(), F, out.data_ptr(), out.stride(0), _extent_bytes(out),
+                lse.data_ptr(), _lib.nbytes(lse), ws_ptr, ws_bytes, _lib.stream_ptr(dev))
+    return out, lse
+
+
+def agnn_backward_dst(csr, x, rn, beta, out, lse, gout):
+    """(alpha [E], bds [E], u [n, F], dbeta [1]) of agnn_aggregate over the same
+    destination CSR: alpha and bds = beta * d score in edge-id order, u = d xn of the
+    rows as destinations (mp_agnn_backward_dst_f32).  No autograd."""
+    nat = _lib.native()
+    x = _nnconv_rows(x, "x")
+    n, F = x.shape
+    dev = x.device
+    beta = _agnn_beta(beta, dev)
+    out, gout = _agnn_rows(out, "out", n, F), _agnn_rows(gout, "gout", n, F)
+    n_ids = max(int(getattr(csr, "n_ids", 0) or 0), csr.n_edges)
+    alpha = torch.empty(n_ids, dtype=torch.float32, device=dev)
+    bds = torch.empty(n_ids, dtype=torch.float32, device=dev)
+    u = torch.empty((n, F), dtype=torch.float32, device=dev)
+    dbeta = torch.zeros(1, dtype=torch.float32, device=dev)
+    ws, ws_ptr, ws_bytes = _agnn_ws(nat, csr, F, _lib.MP_AGNN_PASS_DST, dev)
+    _count_call(nat, "mp_agnn_backward_dst_f32", csr.struct("other"), x.data_ptr(), x.stride(0), _extent_bytes(x),
+                rn.data_ptr(), _lib.nbytes(rn), beta.data_ptr(), F, out.data_ptr(), out.stride(0), _extent_bytes(out),
+                lse.data_ptr(), _lib.nbytes(lse), gout.data_ptr(), gout.stride(0), _extent_bytes(gout),
+                alpha.data_ptr(), _lib.nbytes(alpha), bds.data_ptr(), _lib.nbytes(bds), u.data_ptr(), u.stride(0),
+                _extent_bytes(u), dbeta.data_ptr(), ws_ptr, ws_bytes, _lib.stream_ptr(dev))
+    return alpha, bds, u, dbeta
+
+
+def agnn_backward_src(csr, x, rn, gout, alpha, bds, u):
+    """d x [n, F] over the SOURCE-keyed CSR from the destination pass's alpha, bds and
+    u (mp_agnn_backward_src_f32).  No autograd."""
+    nat = _lib.native()
+    x = _nnconv_rows(x, "x")
+    n, F = x.shape
+    dev = x.device
+    gout, u = _agnn_rows(gout, "gout", n, F), _agnn_rows(u, "u", n, F)
+    dx = torch.empty((n, F), dtype=torch.float32, device=dev)
+    ws, ws_ptr, ws_bytes = _agnn_ws(nat, csr, F, _lib.MP_AGNN_PASS_SRC, dev)
+    _count_call(nat, "mp_agnn_backward_src_f32", csr.struct("other"), x.data_ptr(), x.stride(0), _extent_bytes(x),
+                rn.data_ptr(), _lib.nbytes(rn), F, gout.data_ptr(), gout.stride(0), _extent_bytes(gout),
+                alpha.data_ptr(), _lib.nbytes(alpha), bds.data_ptr(), _lib.nbytes(bds), u.data_ptr(), u.stride(0),
+                _extent_bytes(u), dx.data_ptr(), dx.stride(0), _extent_bytes(dx), ws_ptr, ws_bytes,
+                _lib.stream_ptr(dev))
+    return dx
+
+
+class _AGNNPropagate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, beta, graph):
+        rn = agnn_rnorm(x)
+        out, lse = agnn_aggregate(graph.dst, x, rn, beta)
+        ctx.graph = graph
+        # the cached Graph holds its edge_index weakly and builds the transposed CSR
+        # on first use, in backward: keep the tensor alive until then
+        ctx.save_for_backward(x, beta, rn, out, lse, graph._edge_index())
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, beta, rn, out, lse, _ = ctx.saved_tensors
+        graph = ctx.graph
+        g = g.contiguous()
+        alpha, bds, u, dbeta = agnn_backward_dst(graph.dst, x, rn, beta, out, lse, g)
+        dx = agnn_backward_src(graph.src, x, rn, g, alpha, bds, u) if ctx.needs_input_grad[0] else None
+        return dx, (dbeta.view_as(beta) if ctx.needs_input_grad[1] else None), None
+
+
+def agnn_propagate(graph, x, beta):
+    """out_i = sum_{j -> i} softmax_j(beta cos(x_i, x_j)) x_j
+
+    AGNNConv's propagate on a looped edge list (graph: both CSRs of it): x fp32 [N,
+    F] on the device, beta one fp32 on the device (a parameter or a buffer: read by
+    the kernels, never by the host).  One gather pass: the gathered row gives the
+    score and is the message, so no [E, F] array is built; the backward keeps two
+    scalars per edge between its destination and its source pass.  Deterministic;
+    the source pass is skipped when x needs no gradient, d beta is returned only when
+    beta requires it."""
+    _lib.require_device(x, beta)
+    if x.dim() != 2 or x.dtype != torch.float32:
+        raise TypeError("mi355_mp: x must be float32 [N, F] (got %s %s)" % (x.dtype, tuple(x.shape)))
+    n, F = x.shape
+    if not agnn_ok(F):
+        raise NotImplementedError("mi355_mp: outside the fused AGNN path's limit: F = %d" % F)
+    if n != graph.n_src or n != graph.n_dst:
+        raise ValueError("mi355_mp: %d nodes, the graph %d sources and %d destinations" % (n, graph.n_src, graph.n_dst))
+    return _AGNNPropagate.apply(x, beta, graph)
+
+
+# ---------------------------------------------------------------------------
 # ARMAConv: K stacks, one fused launch per recurrent step (csrc/mp_arma.hip)
 # ---------------------------------------------------------------------------
 
