@@ -1124,6 +1124,55 @@ int64_t mp_agnn_backward_src_f32(const mp_csr* g, const float* x, int64_t ldx, s
                                  const float* u, int64_t ldu, size_t u_bytes, float* dx, int64_t lddx,
                                  size_t dx_bytes, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- Sparse x sparse product: LDS row accumulators (csrc/mp_spgemm.hip)
+ * torch_sparse.spspmm [U]: C = A B for A [m, k], B [k, n] given as the stable row CSRs
+ * of mp_csr_build (rowptr int32 [rows + 1], col and eid int32 [nnz]; values fp32 in the
+ * caller's order, read through eid).  The result is coalesced: distinct (row, col) in
+ * row-major order, an entry whose products cancel kept.  Unsorted inputs and duplicate
+ * entries are taken as they are (a duplicate counts as its sum).  m, k, n, nnz_a, nnz_b
+ * and nnz_c lie in [0, 2^31 - 2]; an index outside its range contributes nothing (the
+ * CSR build counts those).  Every array travels with its extent in bytes, checked
+ * before any launch; a NULL array is accepted where it holds no element.
+ *   mp_spgemm_count: rowptr_c int64 [m + 1] (the scanned distinct columns per row) and
+ *     stats int64 [4] = { nnz(C), rows in the wave bin, the workgroup bin, the window
+ *     bin }, both on the device: the caller reads stats once and sizes the output.
+ *   mp_spgemm_fill_f32: out_row, out_col int64 [nnz_c], out_val fp32 [nnz_c], nnz_c =
+ *     stats[0]; ws is the workspace the count call of the same product filled.
+ * flags: MP_SPGEMM_DROP_DIAG skips every product on column == row in both passes.
+ * Rows are binned by ub = sum over the row's A slots of nnz(B_k): at most
+ * mp_spgemm_bin_cap(MP_SPGEMM_CAP_WAVE) a wave per row with a hash table of at most
+ * MP_SPGEMM_SLOTS_WAVE slots in LDS, at most MP_SPGEMM_CAP_WG a workgroup per row with
+ * at most MP_SPGEMM_SLOTS_WG slots, above that passes over windows of MP_SPGEMM_WINDOW
+ * columns with a dense LDS accumulator and a presence bitmap.  A table has the power of
+ * two >= 2 ub (at least 64) slots and hashes col mod slots with linear probing.  Values
+ * are added in ascending product order (A slot, then B slot) by plain fp32 adds ordered
+ * through integer tags: no float atomics, the same bits on every run.
+ * ws: mp_spgemm_workspace(m) bytes, one layout (csrc/mp_spgemm.hip SpgemmWs).
+ * Additions to ABI 7 that return int64_t like the AGNN calls: the launches enqueued,
+ * >= 0, or -(MP_ERR_* code) with the reason in mp_last_error().  mp_spgemm_bin_cap
+ * (-MP_ERR_ARG for an unknown question) and mp_spgemm_workspace need no GPU. */
+#define MP_SPGEMM_DROP_DIAG 1
+#define MP_SPGEMM_CAP_WAVE 0
+#define MP_SPGEMM_CAP_WG 1
+#define MP_SPGEMM_WINDOW 2
+#define MP_SPGEMM_SLOTS_WAVE 3
+#define MP_SPGEMM_SLOTS_WG 4
+int64_t mp_spgemm_bin_cap(int32_t which);
+size_t mp_spgemm_workspace(int64_t m);
+int64_t mp_spgemm_count(const int32_t* rowptr_a, size_t rowptr_a_bytes, const int32_t* col_a, size_t col_a_bytes,
+                        const int32_t* rowptr_b, size_t rowptr_b_bytes, const int32_t* col_b, size_t col_b_bytes,
+                        int64_t m, int64_t k, int64_t n, int64_t nnz_a, int64_t nnz_b, int32_t flags,
+                        int64_t* rowptr_c, size_t rowptr_c_bytes, int64_t* stats, size_t stats_bytes, void* ws,
+                        size_t ws_bytes, void* stream);
+int64_t mp_spgemm_fill_f32(const int32_t* rowptr_a, size_t rowptr_a_bytes, const int32_t* col_a, size_t col_a_bytes,
+                           const int32_t* eid_a, size_t eid_a_bytes, const float* val_a, size_t val_a_bytes,
+                           const int32_t* rowptr_b, size_t rowptr_b_bytes, const int32_t* col_b, size_t col_b_bytes,
+                           const int32_t* eid_b, size_t eid_b_bytes, const float* val_b, size_t val_b_bytes,
+                           int64_t m, int64_t k, int64_t n, int64_t nnz_a, int64_t nnz_b, int32_t flags,
+                           const int64_t* rowptr_c, size_t rowptr_c_bytes, int64_t nnz_c, int64_t* out_row,
+                           size_t out_row_bytes, int64_t* out_col, size_t out_col_bytes, float* out_val,
+                           size_t out_val_bytes, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- TopKPooling: score, per-graph select, gate, filter_adj (csrc/mp_pool.hip)
  * PyG 1.4.3 nn.pool.topk_pool [U] as one deterministic native path: no atomics
  * on values (two integer counters and one integer maximum aside), no dense

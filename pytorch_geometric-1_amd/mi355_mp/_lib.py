@@ -302,8 +302,17 @@ SIGNATURES = {
                                        c_p, i64, sz, c_p, sz, c_p, sz, c_p, i64, sz, c_p, c_p, sz, c_p]),
     "mp_agnn_backward_src_f32": (i64, [ctypes.POINTER(MpCsr), c_p, i64, sz, c_p, sz, i32, c_p, i64, sz, c_p, sz, c_p,
                                        sz, c_p, i64, sz, c_p, i64, sz, c_p, sz, c_p]),
+    # the sparse product (csrc/mp_spgemm.hip): int64 returns again, the sign tested by ops._count_call
+    "mp_spgemm_bin_cap": (i64, [i32]),             # an answer (a bin limit or a table size), or -MP_ERR_ARG
+    "mp_spgemm_workspace": (sz, [i64]),
+    "mp_spgemm_count": (i64, [c_p, sz, c_p, sz, c_p, sz, c_p, sz, i64, i64, i64, i64, i64, i32, c_p, sz, c_p, sz, c_p,
+                              sz, c_p]),
+    "mp_spgemm_fill_f32": (i64, [c_p, sz, c_p, sz, c_p, sz, c_p, sz, c_p, sz, c_p, sz, c_p, sz, c_p, sz, i64, i64, i64,
+                                 i64, i64, i32, c_p, sz, i64, c_p, sz, c_p, sz, c_p, sz, c_p, sz, c_p]),
 }
 MP_AGNN_PASS_FWD, MP_AGNN_PASS_DST, MP_AGNN_PASS_SRC = 0, 1, 2
+MP_SPGEMM_DROP_DIAG = 1
+MP_SPGEMM_CAP_WAVE, MP_SPGEMM_CAP_WG, MP_SPGEMM_WINDOW, MP_SPGEMM_SLOTS_WAVE, MP_SPGEMM_SLOTS_WG = 0, 1, 2, 3, 4
 MP_NEG_FULL = 0
 MP_NEG_UPPER = 1
 

@@ -4601,3 +4601,101 @@ def structured_negative_sample(edge_index, num_nodes, seed=None):
                     table.n_keys.data_ptr(), table.n_nodes, _sample_seed(seed, dev), row.data_ptr(), E, out.data_ptr(),
                     E * 8, _lib.stream_ptr(dev))
     return out
+
+
+# ---------------------------------------------------------------------------
+# Sparse x sparse product: LDS row accumulators (torch_sparse.spspmm [U]; csrc/mp_spgemm.hip)
+# ---------------------------------------------------------------------------
+
+_SPGEMM_CAPS = {"wave": _lib.MP_SPGEMM_CAP_WAVE, "workgroup": _lib.MP_SPGEMM_CAP_WG, "window": _lib.MP_SPGEMM_WINDOW,
+                "wave_slots": _lib.MP_SPGEMM_SLOTS_WAVE, "workgroup_slots": _lib.MP_SPGEMM_SLOTS_WG}
+
+
+def spgemm_bin_cap(which):
+    """A limit of the sparse product's row bins (mp_spgemm_bin_cap; needs no GPU):
+    'wave' / 'workgroup' = the largest product upper bound ub of a row of that bin,
+    'window' = the columns of one window of the rows above both, 'wave_slots' /
+    'workgroup_slots' = the largest hash table of the bin."""
+    return int(_count_call(_lib.native(), "mp_spgemm_bin_cap", _SPGEMM_CAPS[which]))
+
+
+class SpgemmStats(object):
+    """What the one host read of a product returned: nnz(C) and the rows per bin."""
+    __slots__ = ("nnz", "rows_wave", "rows_workgroup", "rows_window", "launches")
+
+    def __init__(self, nnz, bins, launches):
+        self.nnz, self.launches = nnz, launches
+        self.rows_wave, self.rows_workgroup, self.rows_window = bins
+
+
+def _spgemm_csr(nat, index, rows, cols, what):
+    """(rowptr, col, eid, bad) of the stable row CSR of one operand's [2, nnz] index."""
+    if index.dtype != torch.int64 or index.dim() != 2 or index.shape[0] != 2:
+        raise ValueError("mi355_mp: %s must be int64 [2, nnz] (got %s %s)" % (what, index.dtype, tuple(index.shape)))
+    dev, nnz = index.device, int(index.shape[1])
+    row, col = index[0].contiguous(), index[1].contiguous()
+    rowptr = torch.empty(rows + 1, dtype=torch.int32, device=dev)
+    ccol = torch.empty(nnz, dtype=torch.int32, device=dev)
+    eid = torch.empty(nnz, dtype=torch.int32, device=dev)
+    bad = torch.empty(1, dtype=torch.int32, device=dev)
+    wsb = nat.mp_csr_build_workspace(nnz, rows)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    nat.mp_csr_build(_lib.ptr(row if nnz else None), _lib.ptr(col if nnz else None), nnz, rows, cols, rowptr.data_ptr(),
+                     _lib.ptr(ccol if nnz else None), _lib.ptr(eid if nnz else None), bad.data_ptr(), ws.data_ptr(),
+                     wsb, _lib.stream_ptr(dev))
+    return rowptr, ccol, eid, bad
+
+
+def spgemm(index_a, value_a, index_b, value_b, m, k, n, drop_diagonal=False, want_stats=False):
+    """C = A B for COO operands: (index [2, nnz] int64, value [nnz] float32), coalesced
+    -- distinct (row, col) in ascending row * n + col order, a duplicate input entry
+    counted as its sum, an entry whose products cancel kept -- as torch_sparse.spspmm.
+    drop_diagonal leaves out every entry with row == col (fused into both passes).
+
+    Two stable row CSRs (mp_csr_build), the count pass, one host read (nnz(C), the
+    rows per bin and the CSR builds' range checks together), the fill pass.  No
+    autograd.  An index outside [0, m) x [0, k) or [0, k) x [0, n) raises IndexError."""
+    _lib.require_device(index_a, value_a, index_b, value_b)
+    nat = _lib.native()
+    m, k, n = int(m), int(k), int(n)
+    for v, idx, what in ((value_a, index_a, "valueA"), (value_b, index_b, "valueB")):
+        if v.dtype != torch.float32 or v.dim() != 1 or v.shape[0] != idx.shape[-1]:
+            raise TypeError("mi355_mp: %s must be float32 [nnz] (got %s %s)" % (what, v.dtype, tuple(v.shape)))
+    lim = 2 ** 31 - 2
+    if min(m, k, n) < 0 or max(m, k, n, int(index_a.shape[-1]), int(index_b.shape[-1])) > lim:
+        raise ValueError("mi355_mp: spgemm takes m, k, n and nnz in [0, 2^31 - 2] (got %d, %d, %d; %d and %d entries)"
+                         % (m, k, n, index_a.shape[-1], index_b.shape[-1]))
+    dev = index_a.device
+    st = _lib.stream_ptr(dev)
+    va, vb = value_a.detach().contiguous(), value_b.detach().contiguous()
+    rpa, ca, ea, bad_a = _spgemm_csr(nat, index_a, m, k, "indexA")
+    rpb, cb, eb, bad_b = _spgemm_csr(nat, index_b, k, n, "indexB")
+    nnz_a, nnz_b = int(ca.numel()), int(cb.numel())
+    flags = _lib.MP_SPGEMM_DROP_DIAG if drop_diagonal else 0
+    rpc = torch.empty(m + 1, dtype=torch.int64, device=dev)
+    stats = torch.empty(4, dtype=torch.int64, device=dev)
+    wsb = nat.mp_spgemm_workspace(m)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    nb = _lib.nbytes
+    csrs = (rpa.data_ptr(), nb(rpa), _lib.ptr(ca if nnz_a else None), nb(ca))
+    csrs_b = (rpb.data_ptr(), nb(rpb), _lib.ptr(cb if nnz_b else None), nb(cb))
+    launches = _count_call(nat, "mp_spgemm_count", *csrs, *csrs_b, m, k, n, nnz_a, nnz_b, flags, rpc.data_ptr(),
+                           nb(rpc), stats.data_ptr(), nb(stats), ws.data_ptr(), wsb, st)
+    nnz, b0, b1, b2, n_bad_a, n_bad_b = torch.cat([stats, bad_a.long(), bad_b.long()]).tolist()   # the one host read
+    if n_bad_a or n_bad_b:
+        raise IndexError("mi355_mp: %d entries of A lie outside [%d, %d], %d of B outside [%d, %d]"
+                         % (n_bad_a, m, k, n_bad_b, k, n))
+    if nnz > lim:
+        raise ValueError("mi355_mp: the product has %d entries, above the limit 2^31 - 2" % nnz)
+    index = torch.empty((2, nnz), dtype=torch.int64, device=dev)
+    value = torch.empty(nnz, dtype=torch.float32, device=dev)
+    some = nnz > 0
+    launches += _count_call(
+        nat, "mp_spgemm_fill_f32", *csrs, _lib.ptr(ea if nnz_a else None), nb(ea), _lib.ptr(va if nnz_a else None),
+        nb(va), *csrs_b, _lib.ptr(eb if nnz_b else None), nb(eb), _lib.ptr(vb if nnz_b else None), nb(vb), m, k, n,
+        nnz_a, nnz_b, flags, rpc.data_ptr(), nb(rpc), nnz, _lib.ptr(index[0] if some else None), nnz * 8,
+        _lib.ptr(index[1] if some else None), nnz * 8, _lib.ptr(value if some else None), nb(value), ws.data_ptr(), wsb,
+        st)
+    if want_stats:
+        return index, value, SpgemmStats(nnz, (b0, b1, b2), launches)
+    return index, value

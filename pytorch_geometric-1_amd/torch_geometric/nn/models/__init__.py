@@ -1,3 +1,4 @@
 from .autoencoder import InnerProductDecoder, GAE, VGAE
+from .graph_unet import GraphUNet
 
-__all__ = ["InnerProductDecoder", "GAE", "VGAE"]
+__all__ = ["InnerProductDecoder", "GAE", "VGAE", "GraphUNet"]
