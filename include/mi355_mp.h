@@ -843,6 +843,57 @@ int64_t mp_arma_step_bwd_f32(const mp_csr* g, const float* lap, size_t lap_bytes
                              float* dpre_prev, int64_t ldq, size_t q_bytes, void* ws, size_t ws_bytes,
                              void* stream);
 
+/* ---- GatedGraphConv: the GRU cell in one f32 MFMA kernel (csrc/mp_gru.hip) ----
+ * PyG's nn.conv.GatedGraphConv [U] (Li et al.), one recurrent step: m = A (h W_l),
+ * h' = GRUCell(m, h).  Sum and mean aggregation are linear, so W_l folds into the
+ * input weight: with a = A h, Wc = W_l W_ih^T [C, 3C] and Wh = W_hh^T [C, 3C],
+ *   r  = sigmoid(a Wc_r + h Wh_r + b_r)          b_r = b_ir + b_hr
+ *   z  = sigmoid(a Wc_z + h Wh_z + b_z)          b_z = b_iz + b_hz
+ *   hn =         h Wh_n + b_hn
+ *   n  = tanh(a Wc_n + b_in + r * hn)
+ *   h' = (1 - z) * n + z * h
+ * (the gate order r, z, n of torch.nn.GRUCell's weights).  State rows are [N, P]
+ * fp32, P = mp_gru_width(C) = C rounded up to 16, ld a multiple of 4 and the base
+ * 16-byte aligned; the P - C padding columns of every output are written as
+ * zeros, those of the inputs are never used (they may hold anything).  Limit
+ * (mp_gru_ok != 0; needs no GPU): 1 <= C <= 128.
+ *   mp_gru_pack_f32: the weight image of one step, mp_gru_pack_bytes(C) bytes,
+ *   from wc and wh, each [C, 3C] under a (row, column) stride pair in floats (W_hh^T
+ *   is passed as a view of W_hh: strides (1, C)), and b_ih / b_hh [3C] or NULL
+ *   (zeros).  Each lane's MFMA B operand is contiguous in it, zero past C.
+ *   mp_gru_cell_f32: h' into out [N, ldo >= P]; v_mfma_f32_16x16x4_f32, one wave
+ *   per 16 output columns for all gates, persistent workgroups over 64-row tiles
+ *   (32-row at P > 64) of [a | h] double-buffered through LDS.  With gates != NULL
+ *   it also stores [n | r | z | hn] as [N, ldg >= 4P] for the backward.  out may
+ *   not alias a or h.
+ *   mp_gru_cell_bwd_f32: one elementwise pass from dh' (the gradient of h'), h and
+ *   gates to dG [N, ldq >= 4P] = [dn_pre | dr_pre | dz_pre | dhn_pre] and dh_dir:
+ *     dn_pre  = dh' (1 - z)(1 - n^2)        dr_pre  = dn_pre hn r (1 - r)
+ *     dz_pre  = dh' (h - n) z (1 - z)       dhn_pre = dn_pre r       dh_dir = dh' z
+ *   so dG[:, 0:3P] is the gradient of a Wc (gate order n, r, z) and dG[:, P:4P] that
+ *   of h Wh (r, z, n); the weight, input and bias gradients are GEMMs and column
+ *   sums over those views.
+ * Every array is passed with its extent in bytes and checked before any launch.
+ * fp32, fixed summation order, no atomics: two calls give the same bits.
+ * Additions to ABI 7 that return int64_t like the ARMAConv calls: the launches
+ * enqueued, >= 0, or -(MP_ERR_* code) with the reason in mp_last_error();
+ * mp_gru_width answers a question (or -MP_ERR_ARG outside the limit),
+ * mp_gru_pack_bytes 0 outside it. */
+int64_t mp_gru_ok(int32_t C);
+int64_t mp_gru_width(int32_t C);
+size_t mp_gru_pack_bytes(int32_t C);
+int64_t mp_gru_pack_f32(const float* wc, int64_t wc_rs, int64_t wc_cs, size_t wc_bytes, const float* wh,
+                        int64_t wh_rs, int64_t wh_cs, size_t wh_bytes, const float* b_ih, size_t bi_bytes,
+                        const float* b_hh, size_t bh_bytes, int32_t C, float* pack, size_t pack_bytes,
+                        void* stream);
+int64_t mp_gru_cell_f32(const float* a, int64_t lda, size_t a_bytes, const float* h, int64_t ldh, size_t h_bytes,
+                        int64_t N, int32_t C, const float* pack, size_t pack_bytes, float* out, int64_t ldo,
+                        size_t out_bytes, float* gates, int64_t ldg, size_t g_bytes, void* stream);
+int64_t mp_gru_cell_bwd_f32(const float* dh, int64_t ldd, size_t dh_bytes, const float* h, int64_t ldh,
+                            size_t h_bytes, const float* gates, int64_t ldg, size_t g_bytes, int64_t N, int32_t C,
+                            float* dG, int64_t ldq, size_t q_bytes, float* dh_dir, int64_t ldr, size_t dir_bytes,
+                            void* stream);
+
 /* ---- Attention readout: Set2Set / GlobalAttention (csrc/mp_glob.hip) ---------
  * PyG 1.4.3's nn.glob.Set2Set and nn.glob.GlobalAttention [U] share one step: a
  * softmax of one scalar per node over each graph, then the softmax-weighted sum

@@ -239,6 +239,14 @@ SIGNATURES = {
                                c_p, i64, sz, c_p, i64, sz, c_p, i64, sz, c_p, sz, c_p]),
     "mp_arma_step_bwd_f32": (i64, [ctypes.POINTER(MpCsr), c_p, sz, c_p, i64, sz, c_p, sz, c_p, i64, sz, i32, i32,
                                    c_p, i64, sz, c_p, i64, sz, c_p, sz, c_p]),
+    # GatedGraphConv's GRU cell (csrc/mp_gru.hip): int64 returns again, the sign tested by ops._count_call
+    "mp_gru_ok": (i64, [i32]),                     # an answer (0 or 1), not a status
+    "mp_gru_width": (i64, [i32]),                  # floats of one state row, or -MP_ERR_ARG
+    "mp_gru_pack_bytes": (sz, [i32]),
+    "mp_gru_pack_f32": (i64, [c_p, i64, i64, sz, c_p, i64, i64, sz, c_p, sz, c_p, sz, i32, c_p, sz, c_p]),
+    "mp_gru_cell_f32": (i64, [c_p, i64, sz, c_p, i64, sz, i64, i32, c_p, sz, c_p, i64, sz, c_p, i64, sz, c_p]),
+    "mp_gru_cell_bwd_f32": (i64, [c_p, i64, sz, c_p, i64, sz, c_p, i64, sz, i64, i32, c_p, i64, sz, c_p, i64, sz,
+                                  c_p]),
     # the attention readout (csrc/mp_glob.hip): int64 returns again, the sign tested by ops._count_call
     "mp_readout_path": (i64, [i64, i32]),          # an answer (0, 1 or 2), or -MP_ERR_ARG
     "mp_readout_chunk": (i64, [i32]),              # nodes per chunk of a split graph, or -MP_ERR_ARG

@@ -2825,6 +2825,150 @@ def arma_propagate(graph, x, ws, vs, bias, K, C, T, shared, relu, p, training, w
 
 
 # ---------------------------------------------------------------------------
+# GatedGraphConv: the GRU cell fused into one f32 MFMA kernel (csrc/mp_gru.hip)
+# ---------------------------------------------------------------------------
+
+def gru_ok(C):
+    """Whether C channels lie inside the fused cell's limit (mp_gru_ok; needs no GPU)."""
+    return bool(_lib.native().mp_gru_ok(int(C)))
+
+
+def gru_width(C):
+    """Floats of one state row: C rounded up to 16 (mp_gru_width; needs no GPU)."""
+    P = int(_lib.native().mp_gru_width(int(C)))
+    if P < 0:
+        raise ValueError("mi355_mp: " + _lib.native().mp_last_error().decode(errors="replace"))
+    return P
+
+
+def _gru_rows(t, width, what):
+    t = _nnconv_rows(t, what)
+    if t.shape[1] != width:
+        raise ValueError("mi355_mp: %s must be [rows, %d], got %s" % (what, width, tuple(t.shape)))
+    if t.stride(1) != 1 or t.stride(0) % 4 or t.data_ptr() % 16:
+        t = t.contiguous()
+    return t
+
+
+def _gru_mat(t):
+    return (_lib.ptr(t), t.stride(0) if t is not None else 0, _extent_bytes(t) if t is not None else 0)
+
+
+def _gru_vec(b):
+    return None if b is None else b.detach().to(torch.float32).contiguous()
+
+
+def gru_pack(wc, wh, b_ih, b_hh, C):
+    """The weight image of one step (mp_gru_pack_f32): wc = W_l W_ih^T and wh = W_hh^T, each
+    [C, 3C] under any strides (a transposed view is read in place), b_ih / b_hh [3C] or None."""
+    nat = _lib.native()
+    C = int(C)
+    wc, wh = wc.detach(), wh.detach()
+    if tuple(wc.shape) != (C, 3 * C) or tuple(wh.shape) != (C, 3 * C):
+        raise ValueError("mi355_mp: wc and wh must be [%d, %d], got %s and %s"
+                         % (C, 3 * C, tuple(wc.shape), tuple(wh.shape)))
+    wc, wh = (w if w.dtype == torch.float32 and min(w.stride()) >= 1 else w.to(torch.float32).contiguous()
+              for w in (wc, wh))
+    b_ih, b_hh = _gru_vec(b_ih), _gru_vec(b_hh)
+    n = nat.mp_gru_pack_bytes(C)
+    pack = torch.empty(n // 4, dtype=torch.float32, device=wc.device)
+    _count_call(nat, "mp_gru_pack_f32", wc.data_ptr(), wc.stride(0), wc.stride(1), _extent_bytes(wc), wh.data_ptr(),
+                wh.stride(0), wh.stride(1), _extent_bytes(wh), _lib.ptr(b_ih), _lib.nbytes(b_ih), _lib.ptr(b_hh),
+                _lib.nbytes(b_hh), C, pack.data_ptr(), n, _lib.stream_ptr(wc.device))
+    return pack
+
+
+def gru_cell_forward(a, h, pack, C, want_gates=False, out=None, gates=None):
+    """h' [N, P] of the cell (mp_gru_cell_f32) for a = A h and h, both [N, P = gru_width(C)], and
+    the image of gru_pack; want_gates / gates=: [n | r | z | hn] as [N, 4P] too.  Returns
+    (h', gates or None).  No autograd."""
+    nat = _lib.native()
+    C = int(C)
+    P = gru_width(C)
+    a, h = _gru_rows(a, P, "a"), _gru_rows(h, P, "h")
+    N, dev = a.shape[0], a.device
+    if h.shape[0] != N:
+        raise ValueError("mi355_mp: a has %d rows, h %d" % (N, h.shape[0]))
+    out = torch.empty((N, P), dtype=torch.float32, device=dev) if out is None else out
+    if want_gates and gates is None:
+        gates = torch.empty((N, 4 * P), dtype=torch.float32, device=dev)
+    _count_call(nat, "mp_gru_cell_f32", *_gru_mat(a), *_gru_mat(h), N, C, pack.data_ptr(), _lib.nbytes(pack),
+                *_gru_mat(out), *_gru_mat(gates), _lib.stream_ptr(dev))
+    return out, gates
+
+
+def gru_cell_backward(dh, h, gates, C, dG=None, dh_dir=None):
+    """The cell's elementwise backward (mp_gru_cell_bwd_f32): from dh [N, P], h and the saved gates,
+    dG [N, 4P] = [dn_pre | dr_pre | dz_pre | dhn_pre] and dh_dir = dh * z.  No autograd."""
+    nat = _lib.native()
+    C = int(C)
+    P = gru_width(C)
+    dh, h, gates = _gru_rows(dh, P, "dh"), _gru_rows(h, P, "h"), _gru_rows(gates, 4 * P, "gates")
+    N, dev = dh.shape[0], dh.device
+    dG = torch.empty((N, 4 * P), dtype=torch.float32, device=dev) if dG is None else dG
+    dh_dir = torch.empty((N, P), dtype=torch.float32, device=dev) if dh_dir is None else dh_dir
+    _count_call(nat, "mp_gru_cell_bwd_f32", *_gru_mat(dh), *_gru_mat(h), *_gru_mat(gates), N, C, *_gru_mat(dG),
+                *_gru_mat(dh_dir), _lib.stream_ptr(dev))
+    return dG, dh_dir
+
+
+class _GRUCell(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, h, wc, wh, b_ih, b_hh):
+        C = wc.shape[0]
+        keep = any(ctx.needs_input_grad)
+        out, gates = gru_cell_forward(a, h, gru_pack(wc, wh, b_ih, b_hh, C), C, want_gates=keep)
+        ctx.C = C
+        ctx.save_for_backward(a, h, wc, wh, gates)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        a, h, wc, wh, gates = ctx.saved_tensors
+        C, P = ctx.C, gru_width(ctx.C)
+        need = ctx.needs_input_grad
+        dG, dh_dir = gru_cell_backward(g, h, gates, C)
+        # dG[:, 0:3P] = d(a Wc) in gate order (n, r, z), dG[:, P:4P] = d(h Wh) in (r, z, n): strided views, no copy
+        d_a, d_h = dG[:, :3 * P], dG[:, P:]
+        pad = torch.nn.functional.pad
+
+        def wide(w, order):   # [C, 3C] -> [C, 3P], the gates in `order`, zero columns past C
+            return pad(w.reshape(C, 3, C)[:, order], (0, P - C)).reshape(C, 3 * P)
+
+        def narrow(m, order):   # [C, 3P] in `order` -> [C, 3C] in (r, z, n)
+            return m.view(C, 3, P)[:, order, :C].reshape(C, 3 * C)
+        da = dh = dwc = dwh = dbi = dbh = None
+        if need[0]:
+            da = pad(torch.mm(d_a, wide(wc, [2, 0, 1]).t()), (0, P - C))
+        if need[1]:
+            dh = dh_dir + pad(torch.mm(d_h, wide(wh, [0, 1, 2]).t()), (0, P - C))
+        if need[2]:
+            dwc = narrow(torch.mm(a[:, :C].t(), d_a), [1, 2, 0])
+        if need[3]:
+            dwh = narrow(torch.mm(h[:, :C].t(), d_h), [0, 1, 2])
+        if need[4] or need[5]:
+            dn, dr, dz, dhn = (col_sums(dG[:, k * P:(k + 1) * P])[:C] for k in range(4))
+            dbi = torch.cat([dr, dz, dn]) if need[4] else None
+            dbh = torch.cat([dr, dz, dhn]) if need[5] else None
+        return da, dh, dwc, dwh, dbi, dbh
+
+
+def gru_cell(a, h, wc, wh, b_ih=None, b_hh=None):
+    """GatedGraphConv's GRU cell in one MFMA kernel (mp_gru_cell_f32; csrc/mp_gru.hip), with autograd:
+        r = sigmoid(a wc_r + h wh_r + b_ir + b_hr),   z = sigmoid(a wc_z + h wh_z + b_iz + b_hz)
+        n = tanh(a wc_n + b_in + r * (h wh_n + b_hn)),   h' = (1 - z) * n + z * h
+    a, h: [N, P] fp32, P = gru_width(C), padding columns ignored; wc, wh: [C, 3C] in torch.nn.GRUCell's gate
+    order (for the layer wc = W_l @ W_ih^T, wh = W_hh^T; torch differentiates the product outside);
+    b_ih, b_hh: [3C] or None.  Returns h' [N, P] with zero padding columns.  The gates are stored
+    only when some input needs a gradient."""
+    _lib.require_device(a, h, wc, wh, b_ih, b_hh)
+    C = int(wc.shape[0])
+    if not gru_ok(C):
+        raise NotImplementedError("mi355_mp: outside the fused GRU cell's limit: C = %d" % C)
+    return _GRUCell.apply(a, h, wc, wh, b_ih, b_hh)
+
+
+# ---------------------------------------------------------------------------
 # TopKPooling (PyG 1.4.3 nn.pool.topk_pool [U]; csrc/mp_pool.hip)
 # ---------------------------------------------------------------------------
 

@@ -1,5 +1,5 @@
 from .conv import MessagePassing, GCNConv, GATConv, SAGEConv, GraphConv, ChebConv, AGNNConv, SGConv, GINConv, SplineConv
-from .conv import PointConv, NNConv, RGCNConv, DNAConv, EdgeConv, DynamicEdgeConv, GMMConv, ARMAConv
+from .conv import PointConv, NNConv, RGCNConv, DNAConv, EdgeConv, DynamicEdgeConv, GMMConv, ARMAConv, GatedGraphConv
 from .glob import global_add_pool, global_mean_pool, global_max_pool, Set2Set, GlobalAttention
 from .pool import (TopKPooling, voxel_grid, consecutive_cluster, max_pool, max_pool_x, avg_pool, avg_pool_x, pool_edge,
                    pool_batch, pool_pos, graclus, fps, radius, radius_graph, knn, knn_graph, nearest)
@@ -15,4 +15,4 @@ __all__ = ["MessagePassing", "GCNConv", "GATConv", "SAGEConv", "GraphConv", "Che
            "pool_batch", "pool_pos", "graclus", "fps", "radius", "radius_graph", "PointConv", "NNConv", "Set2Set",
            "GlobalAttention", "DataParallel", "RGCNConv", "DNAConv", "EdgeConv", "DynamicEdgeConv", "knn", "knn_graph",
            "nearest", "knn_interpolate", "DenseSAGEConv", "dense_diff_pool", "InnerProductDecoder", "GAE", "VGAE",
-           "GMMConv", "ARMAConv", "GraphUNet"]
+           "GMMConv", "ARMAConv", "GraphUNet", "GatedGraphConv"]

@@ -15,7 +15,8 @@ from .dna_conv import DNAConv
 from .edge_conv import EdgeConv, DynamicEdgeConv
 from .gmm_conv import GMMConv
 from .arma_conv import ARMAConv
+from .gated_graph_conv import GatedGraphConv
 
 __all__ = ["MessagePassing", "GCNConv", "GATConv", "SAGEConv", "GraphConv", "ChebConv", "AGNNConv", "SGConv", "GINConv",
            "SplineConv", "PointConv", "NNConv", "RGCNConv", "DNAConv", "EdgeConv", "DynamicEdgeConv", "GMMConv",
-           "ARMAConv"]
+           "ARMAConv", "GatedGraphConv"]
