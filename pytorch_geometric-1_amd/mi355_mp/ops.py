@@ -152,7 +152,7 @@ def col_sums(g):
     per-block partials (mp_col_sums_f32) where the row fits 256 features,
     else torch's reduction."""
     n, F = g.shape
-    if g.is_cuda and 0 < F <= 256 and F % 4 == 0 and g.stride(1) == 1 and g.stride(0) % 4 == 0 \
+    if g.is_cuda and n > 0 and 0 < F <= 256 and F % 4 == 0 and g.stride(1) == 1 and g.stride(0) % 4 == 0 \
             and g.data_ptr() % 16 == 0 and g.dtype == torch.float32:
         nat = _lib.native()
         part = torch.empty((int(nat.mp_gat_bwd_blocks(n)), F), dtype=torch.float32, device=g.device)
@@ -2280,8 +2280,9 @@ def dna_aggregate(csr, q, k, v, norm, heads, p=0.0, seed=0, out=None, want_lse=F
     n_ids = max(int(getattr(csr, "n_ids", 0) or 0), csr.n_edges)
     lse = torch.empty((n_ids, H), dtype=torch.float32, device=dev) if want_lse else None
     ws, ws_ptr, ws_bytes = _dna_ws(nat, csr, C, dev)
-    _count_call(nat, "mp_dna_aggregate_f32", *args, T, H, C, *_dna_drop(p, seed), out.data_ptr(), out.stride(0),
-                _extent_bytes(out), _lib.ptr(lse), _lib.nbytes(lse), ws_ptr, ws_bytes, _lib.stream_ptr(dev))
+    if csr.n_rows:      # (no rows: nothing to write, and an empty tensor has no address to pass)
+        _count_call(nat, "mp_dna_aggregate_f32", *args, T, H, C, *_dna_drop(p, seed), out.data_ptr(), out.stride(0),
+                    _extent_bytes(out), _lib.ptr(lse), _lib.nbytes(lse), ws_ptr, ws_bytes, _lib.stream_ptr(dev))
     return (out, lse) if want_lse else out
 
 
@@ -2295,9 +2296,10 @@ def dna_backward_dst(csr, q, k, v, norm, gout, lse, heads, p=0.0, seed=0, out=No
     if out is None:
         out = torch.empty((csr.n_rows, C), dtype=torch.float32, device=dev)
     ws, ws_ptr, ws_bytes = _dna_ws(nat, csr, C, dev)
-    _count_call(nat, "mp_dna_backward_dst_f32", *args, gout.data_ptr(), gout.stride(0), _extent_bytes(gout),
-                lse.data_ptr(), _lib.nbytes(lse), T, H, C, *_dna_drop(p, seed), out.data_ptr(), out.stride(0),
-                _extent_bytes(out), ws_ptr, ws_bytes, _lib.stream_ptr(dev))
+    if csr.n_rows:      # (no rows: nothing to write, and an empty tensor has no address to pass)
+        _count_call(nat, "mp_dna_backward_dst_f32", *args, gout.data_ptr(), gout.stride(0), _extent_bytes(gout),
+                    lse.data_ptr(), _lib.nbytes(lse), T, H, C, *_dna_drop(p, seed), out.data_ptr(), out.stride(0),
+                    _extent_bytes(out), ws_ptr, ws_bytes, _lib.stream_ptr(dev))
     return out
 
 
@@ -2318,10 +2320,11 @@ def dna_backward_src(csr, q, k, v, norm, gout, lse, heads, p=0.0, seed=0, dk=Non
                 (t.numel() and (t.stride(2) != 1 or t.stride(1) != C or t.stride(0) < T * C)):
             raise ValueError("mi355_mp: %s must be float32 [%d, %d, %d] with rows of T*C floats" % (what, csr.n_rows, T, C))
     ws, ws_ptr, ws_bytes = _dna_ws(nat, csr, 2 * T * C, dev)
-    _count_call(nat, "mp_dna_backward_src_f32", *args, gout.data_ptr(), gout.stride(0), _extent_bytes(gout),
-                lse.data_ptr(), _lib.nbytes(lse), T, H, C, *_dna_drop(p, seed), dk.data_ptr(), dk.stride(0),
-                _extent_bytes(dk), dv.data_ptr(), dv.stride(0), _extent_bytes(dv), ws_ptr, ws_bytes,
-                _lib.stream_ptr(dev))
+    if csr.n_rows:      # (no rows: nothing to write, and an empty tensor has no address to pass)
+        _count_call(nat, "mp_dna_backward_src_f32", *args, gout.data_ptr(), gout.stride(0), _extent_bytes(gout),
+                    lse.data_ptr(), _lib.nbytes(lse), T, H, C, *_dna_drop(p, seed), dk.data_ptr(), dk.stride(0),
+                    _extent_bytes(dk), dv.data_ptr(), dv.stride(0), _extent_bytes(dv), ws_ptr, ws_bytes,
+                    _lib.stream_ptr(dev))
     return dk, dv
 
 
@@ -2892,8 +2895,9 @@ def gru_cell_forward(a, h, pack, C, want_gates=False, out=None, gates=None):
     out = torch.empty((N, P), dtype=torch.float32, device=dev) if out is None else out
     if want_gates and gates is None:
         gates = torch.empty((N, 4 * P), dtype=torch.float32, device=dev)
-    _count_call(nat, "mp_gru_cell_f32", *_gru_mat(a), *_gru_mat(h), N, C, pack.data_ptr(), _lib.nbytes(pack),
-                *_gru_mat(out), *_gru_mat(gates), _lib.stream_ptr(dev))
+    if N:           # (an empty tensor has no address to pass)
+        _count_call(nat, "mp_gru_cell_f32", *_gru_mat(a), *_gru_mat(h), N, C, pack.data_ptr(), _lib.nbytes(pack),
+                    *_gru_mat(out), *_gru_mat(gates), _lib.stream_ptr(dev))
     return out, gates
 
 
@@ -2907,8 +2911,9 @@ def gru_cell_backward(dh, h, gates, C, dG=None, dh_dir=None):
     N, dev = dh.shape[0], dh.device
     dG = torch.empty((N, 4 * P), dtype=torch.float32, device=dev) if dG is None else dG
     dh_dir = torch.empty((N, P), dtype=torch.float32, device=dev) if dh_dir is None else dh_dir
-    _count_call(nat, "mp_gru_cell_bwd_f32", *_gru_mat(dh), *_gru_mat(h), *_gru_mat(gates), N, C, *_gru_mat(dG),
-                *_gru_mat(dh_dir), _lib.stream_ptr(dev))
+    if N:
+        _count_call(nat, "mp_gru_cell_bwd_f32", *_gru_mat(dh), *_gru_mat(h), *_gru_mat(gates), N, C, *_gru_mat(dG),
+                    *_gru_mat(dh_dir), _lib.stream_ptr(dev))
     return dG, dh_dir
 
 

@@ -11,8 +11,9 @@ that is the message, so one fused HIP pass per destination row gathers each x_j
 once, takes the dot product and the online softmax from it and adds it into the
 output from the same registers (mi355_mp.ops.agnn_propagate: csrc/mp_agnn.hip),
 forward and backward, deterministic; no [E, F] array exists, and beta is read on
-the device.  The fused path is taken for device fp32 contiguous 2-D x with at
-least one node, node_dim 0, message / update / aggregate not overridden and F
+the device.  The fused path is taken for device fp32 2-D x with at least one
+node (a non-contiguous view is copied once, so a view and its contiguous clone
+give the same bits), node_dim 0, message / update / aggregate not overridden and F
 inside ops.agnn_ok; it serves both flows, the learned beta and the beta buffer.
 The looped edge list is cached on the caller's edge_index (_structure.gat_loops),
 so graph_for meets the same tensor on every call.  Everything else (float64, a
@@ -57,7 +58,7 @@ class AGNNConv(MessagePassing):
             return False
         beta = self._beta()
         if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2
-                and x.is_contiguous() and x.size(0) > 0 and x.size(1) > 0):
+                and x.size(0) > 0 and x.size(1) > 0):
             return False
         if not (edge_index.is_cuda and beta.dtype == torch.float32 and beta.device == x.device):
             return False
@@ -70,7 +71,9 @@ class AGNNConv(MessagePassing):
             edge_index = gat_loops(edge_index, n)
             # tasks of at least agnn_split_chunk() units: the kernels then split long rows on a graph of any size
             graph = graph_for(edge_index, n, n, self.flow, _ops.agnn_target_tasks(n, edge_index.size(1)))
-            return _ops.agnn_propagate(graph, x, self._beta())
+            # one contiguous x whatever the view: the kernels' lane mapping (vec4 or scalar) follows the rows'
+            # alignment, so a view would be summed in another order than its own copy
+            return _ops.agnn_propagate(graph, x.contiguous(), self._beta())
         edge_index, _ = remove_self_loops(edge_index)
         edge_index, _ = add_self_loops(edge_index, num_nodes=x.size(self.node_dim))
         x_norm = F.normalize(x, p=2, dim=-1)

@@ -60,13 +60,17 @@ def gradients(x, edge_index, edge_weight, ws, vs, bias, T, shared, g, act="relu"
 
 
 def assert_bound(got, ref, scale, what):
-    """|got - ref| <= 1e-5 * scale elementwise (scale = sum |terms|); prints the largest ratio."""
+    """|got - ref| <= 1e-5 * scale elementwise (scale = sum |terms|); prints and returns the largest ratio
+    |err| / sum |terms| (0.0 for an empty tensor)."""
     assert tuple(got.shape) == tuple(ref.shape) == tuple(scale.shape), "%s: shapes %s / %s / %s" % (
         what, tuple(got.shape), tuple(ref.shape), tuple(scale.shape))
     assert bool(torch.isfinite(got.detach()).all()), "%s: non-finite entries" % what
+    if got.numel() == 0:
+        return 0.0
     err = (got.detach().cpu().double() - ref.detach()).abs()
     lim = BOUND * scale.detach()
     worst = float((err - lim).max())
     ratio = float((err / scale.detach().clamp(min=1e-300)).max())
     print("%s: max |err| / sum|terms| = %.3g" % (what, ratio))
     assert worst <= 0.0, "%s: |err| exceeds 1e-5 * sum|terms| by %.3g (max ratio %.3g)" % (what, worst, ratio)
+    return ratio

@@ -1,7 +1,8 @@
 """Input generators shared by the CPU and the GPU fuzz tests of SplineConv,
-TopKPooling, cluster pooling, NNConv and RGCNConv (tests/test_fuzz_cases_host.py,
+TopKPooling, cluster pooling, NNConv, RGCNConv, ARMAConv and GatedGraphConv
+(tests/test_fuzz_cases_host.py, tests/test_recurrent_cases_host.py,
 tests/test_gpu_fuzz_pool_layers.py, tests/test_gpu_fuzz_layers.py,
-tests/test_gpu_fuzz_conv_layers.py).
+tests/test_gpu_fuzz_conv_layers.py, tests/test_gpu_fuzz_recurrent_layers.py).
 
 Plain torch on the CPU: every generator takes simple parameters plus a seed and
 returns CPU tensors, so a failing example replays from its arguments alone.
@@ -260,3 +261,73 @@ def rgcn_inputs(p):
     E = ei.shape[1]
     x = None if p["mode"] == "featureless" else torch.randn(p["N"], p["c_in"], generator=g)
     return ei, x, relations(p["rkind"], E, p["R"], p["seed"]), edge_norm(p["nkind"], E, p["seed"])
+
+
+# ---- ARMAConv and GatedGraphConv (tests/test_gpu_fuzz_recurrent_layers.py) -------------------------------------
+
+def _ar(N, deg, loops, F_in, kc, T, shared, act, bias, weighted, form, seed):
+    return dict(N=N, deg=deg, loops=loops, F_in=F_in, kc=kc, T=T, shared=shared, act=act, bias=bias,
+                weighted=weighted, form=form, seed=seed)
+
+
+# The pinned examples of test_fuzz_armaconv_layer: N = 1 without edges and with self loops only; E = 0 at N = 5;
+# every edge a loop; deg 0.3 (mostly isolated nodes); one example per task width L = 4, 8, 16, 32, 64; T = 3 with
+# K = 1 (the in-kernel transform without a mean); C = 1
+ARMA_PINNED = (
+    _ar(1, 0.0, 0.0, 3, (3, 5), 2, False, "relu", True, True, None, 1),
+    _ar(1, 3.0, 1.0, 2, (1, 12), 2, True, "relu", True, False, "fused", 2),
+    _ar(5, 0.0, 0.0, 7, (5, 4), 3, False, None, True, True, "fused", 3),
+    _ar(40, 4.0, 1.0, 6, (3, 7), 2, True, "relu", True, True, None, 4),
+    _ar(60, 0.3, 0.0, 5, (9, 4), 2, False, "relu", True, False, "fused", 5),
+    _ar(70, 4.0, 0.2, 9, (2, 2), 2, False, "relu", True, True, "fused", 6),
+    _ar(70, 4.0, 0.2, 20, (1, 32), 2, True, None, False, True, "fused", 7),
+    _ar(70, 4.0, 0.2, 4, (7, 9), 3, False, "relu", True, True, "fused", 8),
+    _ar(70, 4.0, 0.2, 11, (5, 13), 2, True, "relu", False, False, "fused", 9),
+    _ar(70, 4.0, 0.2, 3, (17, 15), 2, False, "relu", True, True, None, 10),
+    _ar(50, 6.0, 0.2, 8, (1, 64), 3, False, "relu", True, True, "fused", 11),
+    _ar(50, 6.0, 0.2, 1, (256, 1), 2, True, "relu", True, False, "fused", 12),
+    _ar(30, 4.0, 0.0, 5, (4, 64), 2, False, "relu", True, True, None, 13),
+)
+
+
+def arma_inputs(p):
+    """(edge_index, edge_weight in [0.5, 1.5) or None, x [N, F_in], ws, vs, bias or None, gout [N, C]) of one
+    test_fuzz_armaconv_layer draw: ARMAConv's parameter lists, random (0.5 * randn, so a bias is nonzero)."""
+    ei, g = conv_graph(p["N"], p["deg"], p["loops"], p["seed"])
+    (K, C), T, F, shared = p["kc"], p["T"], p["F_in"], p["shared"]
+    ew = torch.rand(ei.shape[1], generator=g) + 0.5 if p["weighted"] else None
+    x = torch.randn(p["N"], F, generator=g)
+    rnd = lambda *s: torch.randn(*s, generator=g) * 0.5  # noqa: E731
+    ws = [rnd(K, F, C)] + [rnd(K, C, C) for _ in range(min(1, T - 1) if shared else T - 1)]
+    n_skip = 1 if shared else T
+    vs = [rnd(K, F, C) for _ in range(n_skip)]
+    bias = [rnd(K, 1, C) for _ in range(n_skip)] if p["bias"] else None
+    return ei, ew, x, ws, vs, bias, torch.randn(p["N"], C, generator=g)
+
+
+def _gg(N, deg, loops, C, L, xcols, aggr, bias, flow, weighted, seed):
+    return dict(N=N, deg=deg, loops=loops, C=C, L=L, xcols=xcols, aggr=aggr, bias=bias, flow=flow, weighted=weighted,
+                seed=seed)
+
+
+# The pinned examples of test_fuzz_gatedgraphconv_layer: N = 1 (a 1-D x); E = 0; C = 1; C = 128 with x 128 wide
+# (the state is x itself, no padding); bias=False with mean; both flows
+GGC_PINNED = (
+    _gg(1, 0.0, 0.0, 16, 2, 0, "add", True, FLOWS[0], False, 1),
+    _gg(1, 3.0, 1.0, 5, 3, 2, "mean", True, FLOWS[1], True, 2),
+    _gg(5, 0.0, 0.0, 40, 2, 9, "mean", True, FLOWS[0], True, 3),
+    _gg(40, 4.0, 0.2, 1, 3, 1, "add", True, FLOWS[1], True, 4),
+    _gg(70, 4.0, 0.2, 128, 2, 128, "add", True, FLOWS[0], True, 5),
+    _gg(60, 3.0, 0.2, 90, 2, 90, "mean", False, FLOWS[1], False, 6),
+    _gg(150, 8.0, 1.0, 100, 1, 33, "add", False, FLOWS[0], True, 7),
+)
+
+
+def ggc_inputs(p):
+    """(edge_index, edge_weight in [0.25, 1.25) or None, x, gout [N, C]) of one test_fuzz_gatedgraphconv_layer
+    draw; xcols = 0: x is 1-D [N], otherwise [N, min(xcols, C)]."""
+    ei, g = conv_graph(p["N"], p["deg"], p["loops"], p["seed"])
+    ew = torch.rand(ei.shape[1], generator=g) + 0.25 if p["weighted"] else None
+    shape = (p["N"],) if p["xcols"] == 0 else (p["N"], min(p["xcols"], p["C"]))
+    x = torch.randn(*shape, generator=g)
+    return ei, ew, x, torch.randn(p["N"], p["C"], generator=g)

@@ -63,13 +63,62 @@ def _stacked(h, K, C):
     return _k(h, K, C)
 
 
-def _nan_rows(K, C, fill=False):
-    """A NaN-filled [N, P] buffer (an unwritten element fails every comparison); fill: random valid columns."""
+def _nan_rows(K, C, fill=False, n=N):
+    """A NaN-filled [n, P] buffer (an unwritten element fails every comparison); fill: random valid columns."""
     from mi355_mp import ops
-    t = torch.full((N, ops.arma_width(K, C)), float("nan"), device=DEV)
+    t = torch.full((n, ops.arma_width(K, C)), float("nan"), device=DEV)
     if fill:
-        t[:, :K * C] = torch.randn(N, K * C, device=DEV)
+        t[:, :K * C] = torch.randn(n, K * C, device=DEV)
     return t
+
+
+def check_forward_steps(edges, graph, lap, K, C, act, w_nexts=(None,), lap64=None, what=""):
+    """Single forward steps (ops.arma_step) into NaN-filled outputs against the reference's aggregation, one per
+    entry of w_nexts: a [K, C, C] next transform (the result is Y_{t+1}) or None (the last step: the mean over
+    the stacks).  edges: the CPU edge_index; graph: keyed on edges[0]; lap: fp32 [E] on the device in edge
+    order; lap64: the reference's weights (default: lap itself).  Returns the largest |err| / sum |terms|."""
+    from mi355_mp import ops
+    n = graph.n_dst
+    lap64 = lap.cpu().double() if lap64 is None else lap64
+    Y, S = _nan_rows(K, C, True, n), _nan_rows(K, C, True, n)
+    pre = R.aggregate(edges, lap64, _k(Y, K, C)) + _k(S, K, C)
+    pre_abs = R.aggregate(edges, lap64, _k(Y, K, C).abs()) + _k(S, K, C).abs()
+    h_ref = pre.clamp(min=0) if act else pre
+    worst = 0.0
+    for w in w_nexts:
+        o, h = ops.arma_step(graph.dst, graph.dst.to_csr_order(lap), Y, S, K, C, act is not None, w,
+                             out=_nan_rows(K, C, n=n)[:, :C].contiguous() if w is None else _nan_rows(K, C, n=n),
+                             hidden=_nan_rows(K, C, n=n))
+        worst = max(worst, R.assert_bound(_stacked(h, K, C), h_ref, pre_abs, "step H %s" % (what,)))
+        if w is None:
+            worst = max(worst, R.assert_bound(o, h_ref.mean(0), pre_abs.mean(0), "step out %s" % (what,)))
+        else:
+            w64 = w.cpu().double()
+            worst = max(worst, R.assert_bound(_stacked(o, K, C), h_ref @ w64, pre_abs @ w64.abs(),
+                                              "step Y %s" % (what,)))
+    return worst
+
+
+def check_backward_step(edges, graph, lap, K, C, act, w=None, h=None, lap64=None, what=""):
+    """One backward step (ops.arma_step_backward) into NaN-filled outputs against the reference's transposed
+    aggregation; w [K, C, C]: the step's transform (dPre of the step before is checked too), h: with act and
+    w, the stacked hidden state whose sign is the mask.  Returns the largest |err| / sum |terms|."""
+    from mi355_mp import ops
+    n = graph.n_src
+    lap64 = lap.cpu().double() if lap64 is None else lap64
+    masked = bool(act) and w is not None and h is not None
+    dpre = _nan_rows(K, C, True, n)
+    dy, prev = ops.arma_step_backward(graph.src, graph.src.to_csr_order(lap), dpre, K, C,
+                                      None if w is None else w.transpose(1, 2), h if masked else None,
+                                      dy=_nan_rows(K, C, n=n), out=None if w is None else _nan_rows(K, C, n=n))
+    dy_ref = R.aggregate(edges, lap64, _k(dpre, K, C), True)
+    dy_abs = R.aggregate(edges, lap64, _k(dpre, K, C).abs(), True)
+    worst = R.assert_bound(_stacked(dy, K, C), dy_ref, dy_abs, "step dY %s" % (what,))
+    if w is not None:
+        wt, m = w.cpu().double().transpose(1, 2), ((_k(h, K, C) > 0) if masked else 1)
+        worst = max(worst, R.assert_bound(_stacked(prev, K, C), (dy_ref @ wt) * m, (dy_abs @ wt.abs()) * m,
+                                          "step dPre %s" % (what,)))
+    return worst
 
 
 def _gpu_masks(Hs, pres, abs_pres, K, C):
@@ -99,7 +148,6 @@ def _propagate(c, case, act, want_hidden=True):
 @pytest.mark.parametrize("act", ["relu", None])
 @pytest.mark.parametrize("case", CASES)
 def test_forward_matches_the_reference(case, act):
-    from mi355_mp import ops
     K, C, T, shared, _ = case
     c = _case(case, act)
     (out, Hs), graph, lap = _propagate(c, case, act)
@@ -111,20 +159,8 @@ def test_forward_matches_the_reference(case, act):
     assert torch.equal(out, out2) and all(torch.equal(a, b) for a, b in zip(Hs, Hs2))
     assert torch.equal(c["layer"](c["x"].to(DEV), c["ei"].to(DEV), c["ew"].to(DEV), form="fused"), out)
     # single steps into NaN-filled outputs: the last step and, with T > 1, one with the in-kernel transform
-    lap64, Y, S = R.laplacian(c["ei"], N, c["ew"]), _nan_rows(K, C, True), _nan_rows(K, C, True)
-    pre = R.aggregate(c["ei"], lap64, _k(Y, K, C)) + _k(S, K, C)
-    pre_abs = R.aggregate(c["ei"], lap64, _k(Y, K, C).abs()) + _k(S, K, C).abs()
-    h_ref = pre.clamp(min=0) if act else pre
-    for w in ([c["layer"].ws[1].detach(), None] if T > 1 else [None]):
-        o, h = ops.arma_step(graph.dst, graph.dst.to_csr_order(lap), Y, S, K, C, act is not None, w,
-                             out=_nan_rows(K, C)[:, :C].contiguous() if w is None else _nan_rows(K, C),
-                             hidden=_nan_rows(K, C))
-        R.assert_bound(_stacked(h, K, C), h_ref, pre_abs, "step H %s" % (case,))
-        if w is None:
-            R.assert_bound(o, h_ref.mean(0), pre_abs.mean(0), "step out %s" % (case,))
-        else:
-            w64 = w.cpu().double()
-            R.assert_bound(_stacked(o, K, C), h_ref @ w64, pre_abs @ w64.abs(), "step Y %s" % (case,))
+    check_forward_steps(c["ei"], graph, lap, K, C, act, [c["layer"].ws[1].detach(), None] if T > 1 else [None],
+                        lap64=R.laplacian(c["ei"], N, c["ew"]), what=case)
 
 
 @pytest.mark.parametrize("act", ["relu", None])
@@ -138,18 +174,8 @@ def test_backward_matches_the_reference(case, act):
     (_, Hs), graph, lap = _propagate(c, case, act)
     layer(x, c["ei"].to(DEV), c["ew"].to(DEV), form="fused").backward(c["gout"].to(DEV))
     # one backward step into NaN-filled outputs against the reference's transposed aggregation
-    from mi355_mp import ops
-    dpre, w = _nan_rows(K, C, True), (layer.ws[1].detach() if T > 1 else None)
-    dy, prev = ops.arma_step_backward(graph.src, graph.src.to_csr_order(lap), dpre, K, C,
-                                      None if w is None else w.transpose(1, 2), Hs[0] if act and T > 1 else None,
-                                      dy=_nan_rows(K, C), out=None if w is None else _nan_rows(K, C))
-    lap64 = R.laplacian(c["ei"], N, c["ew"])
-    dy_ref = R.aggregate(c["ei"], lap64, _k(dpre, K, C), True)
-    dy_abs = R.aggregate(c["ei"], lap64, _k(dpre, K, C).abs(), True)
-    R.assert_bound(_stacked(dy, K, C), dy_ref, dy_abs, "step dY %s" % (case,))
-    if w is not None:
-        wt, m = w.cpu().double().transpose(1, 2), ((_k(Hs[0], K, C) > 0) if act else 1)
-        R.assert_bound(_stacked(prev, K, C), (dy_ref @ wt) * m, (dy_abs @ wt.abs()) * m, "step dPre %s" % (case,))
+    check_backward_step(c["ei"], graph, lap, K, C, act, layer.ws[1].detach() if T > 1 else None, Hs[0],
+                        lap64=R.laplacian(c["ei"], N, c["ew"]), what=case)
     masks = _gpu_masks(Hs, c["ref"][2], c["abs"][2], K, C) if act == "relu" else None
     args = c["args"] + (c["gout"],)
     ref = R.gradients(*args, act=act, masks=masks)
